@@ -1,6 +1,6 @@
 """bench.py — device-resident WebSocket unmask throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N ... bench.py --gpus N   (one rank per GPU, RCCL)
 
 A step = one websocketframeBatchDecodeDevice call over the whole synthetic batch
@@ -11,6 +11,13 @@ in HBM. value = payload GiB/s over all ranks (weak scaling: rank r decodes frame
 path — RCCL only carries the max-over-ranks time, counts and the output hash).
 roofline.frac is the step's (the contract's timed region: walk + unmask); the unmask
 kernel alone is reported as roofline.kernel_frac.
+
+A plain run sets up, warms up, times the steps, checks the decoded batch against the generator
+and prints the line. --full adds everything else the line can carry: the CPU baselines
+(cpu_baseline), the XOR-stream reference (xor_stream), the dominant kernel's own launch time
+(roofline.kernel_frac from a second region of calls), the host-buffer end-to-end run (e2e) and
+the other single-GPU paths (paths). --dump-outputs DIR writes what the last timed step left
+with the caller as DIR/<name>.npy (dump_decoded), for comparing two builds output by output.
 
 --config cfg4: BASELINE configs[3] as STRONG scaling — ONE global batch of 8 M x 64 KiB
 frames (549.9 GB of wire) sharded over the ranks by segment ranges, each rank generating
@@ -86,6 +93,75 @@ def timed_region(step, steps, world):
     if world > 1:
         dist.barrier()
     return time.perf_counter() - t0, e0.elapsed_time(e1) / steps
+
+
+DUMP_SUMS_MAX = 1 << 20        # --dump-outputs: byte sums of at most this many chunks of a buffer
+DUMP_SAMPLE_BYTES = 4 << 20    # ... single bytes at this many seeded positions
+DUMP_ROWS_MAX = 1 << 17        # ... descriptors of at most this many (seeded) frames
+
+
+def _dump_rows(n, cap, seed):
+    """row indices to dump: all n, or a fixed seeded sample of about cap of them (ascending)"""
+    if n <= cap:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, cap))
+
+
+def dump_sample_positions(nbytes):
+    """the seeded byte positions of <name>_sample.npy in a buffer of nbytes bytes (ascending)"""
+    return np.sort(np.random.default_rng(0x5EED).integers(0, max(nbytes, 1), min(nbytes, DUMP_SAMPLE_BYTES)))
+
+
+def dump_bytes(dirpath, name, t, nbytes, torch):
+    """<name>_chunk_sums.npy: the byte sum of every chunk of t[:nbytes] (a device uint8 buffer;
+    chunks of 4 KiB, doubled until at most DUMP_SUMS_MAX of them; float64, exact; the last chunk
+    may be short), so every byte of the buffer counts. <name>_sample.npy: the bytes at
+    DUMP_SAMPLE_BYTES seeded positions (float32)."""
+    chunk = 4096
+    while (nbytes + chunk - 1) // chunk > DUMP_SUMS_MAX:
+        chunk *= 2
+    whole = nbytes // chunk
+    sums = torch.empty((nbytes + chunk - 1) // chunk, dtype=torch.int64, device=t.device)
+    slab = max(1, (256 << 20) // chunk)      # chunks per reduction: bounds the reduction's temporaries
+    for c0 in range(0, whole, slab):
+        c1 = min(whole, c0 + slab)
+        sums[c0:c1] = t[c0 * chunk:c1 * chunk].view(c1 - c0, chunk).sum(dim=1, dtype=torch.int64)
+    if whole < len(sums):
+        sums[whole] = t[whole * chunk:nbytes].sum(dtype=torch.int64)
+    np.save(os.path.join(dirpath, name + "_chunk_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    smp = t[torch.from_numpy(dump_sample_positions(nbytes)).to(t.device)]
+    np.save(os.path.join(dirpath, name + "_sample.npy"), smp.cpu().numpy().astype(np.float32))
+
+
+def dump_decoded(dirpath, rank, buf, nbytes, desc, res, nseg, fps):
+    """--dump-outputs of a decode call (batch: nseg segments of fps descriptor slots; one raw
+    stream: nseg = 1, fps = its descriptor slots): what the caller holds after the last timed
+    call. wire_*: the buffer decoded in place (dump_bytes). desc.npy: frame_off, data_off,
+    datalen, ret, is_fin, type, masked, hdrlen of every frame (or a seeded sample of
+    DUMP_ROWS_MAX; slots past a segment's n_frames are unspecified and dumped as 0).
+    seg_results.npy: consumed, n_frames, status of every segment. All float64 (exact: < 2^53).
+    Rank r > 0 of a multi-rank run writes rank<r>_<name>.npy."""
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    pre = "rank%d_" % rank if rank else ""
+    torch.cuda.synchronize()
+    dump_bytes(dirpath, pre + "wire", buf, nbytes, torch)
+    r = res[:nseg * 16].view(torch.int64).view(nseg, 2)
+    nfr = r[:, 1] & 0xFFFFFFFF
+    rows = _dump_rows(nseg * fps, DUMP_ROWS_MAX, 0xD5C)
+    slot = torch.arange(nseg * fps, device=buf.device) if rows is None else torch.from_numpy(rows).to(buf.device)
+    d = desc[:nseg * fps * 32].view(torch.int64).view(nseg * fps, 4)[slot]
+    used = (slot % fps) < nfr[slot // fps]
+    rest = d[:, 3]
+    cols = [d[:, 0], d[:, 1], d[:, 2], (rest & 0xFFFFFFFF) - ((rest & 0x80000000) << 1)] + \
+           [(rest >> s) & 0xFF for s in (32, 40, 48, 56)]
+    out = torch.stack(cols, dim=1) * used[:, None]
+    np.save(os.path.join(dirpath, pre + "desc.npy"), out.cpu().numpy().astype(np.float64))
+    rr = _dump_rows(nseg, DUMP_SUMS_MAX, 0x5E6)
+    if rr is not None:
+        r = r[torch.from_numpy(rr).to(buf.device)]
+    sr = torch.stack([r[:, 0], r[:, 1] & 0xFFFFFFFF, r[:, 1] >> 32], dim=1)
+    np.save(os.path.join(dirpath, pre + "seg_results.npy"), sr.cpu().numpy().astype(np.float64))
 
 
 def pmc_traffic(kernel, algo_bytes, metric, graph=None):
@@ -306,6 +382,13 @@ def run_encode(args, dev, world, rank):
         wl.step()
     torch.cuda.synchronize()
     wall, step_ms = timed_region(wl.step, args.steps, world)
+    if args.dump_outputs:                  # the encoded wire and the frames' offsets in it
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        pre = "rank%d_" % rank if rank else ""
+        dump_bytes(args.dump_outputs, pre + "wire", wl.dst, wl.wire_bytes, torch)
+        rows = _dump_rows(wl.nframes + 1, DUMP_SUMS_MAX, 0x0FF)
+        off = wl.off if rows is None else wl.off[torch.from_numpy(rows).to(dev)]
+        np.save(os.path.join(args.dump_outputs, pre + "frame_off.npy"), off.cpu().numpy().astype(np.float64))
     elapsed = D.allreduce([wall], op="max", device=dev)[0]
     kern_ms = np.array([step_ms])
     mism = int(D.allreduce([wl.verify()], device=dev)[0])
@@ -333,7 +416,7 @@ def run_encode(args, dev, world, rank):
         "verified": mism == 0,
         "output_hash": "%016x" % D.allreduce_u64([wl.hash], device=dev)[0],
         "cpu_baseline": cpu_encode_baseline(wl, args.cpu_threads or granted_cpus()[0])
-        if rank == 0 and world == 1 and not args.no_cpu else None,
+        if rank == 0 and world == 1 and args.full and not args.no_cpu else None,
     }
     if getattr(args, "cpu_defer", False):      # run_paths: timed on the CPU after every GPU path
         out["_cpu_later"] = (lambda smp=encode_cpu_sample(wl): cpu_encode_baseline(
@@ -437,6 +520,8 @@ def run_stream(args, dev, world, rank):
         step()
     torch.cuda.synchronize()
     wall, step_ms = timed_region(step, args.steps, world)
+    if args.dump_outputs:
+        dump_decoded(args.dump_outputs, rank, wl.buf, wl.wire_bytes, wl.desc, res, 1, wl.nframes)
     elapsed = D.allreduce([wall], op="max", device=dev)[0]
     r = res.cpu().numpy().view(W.SEGRES_DTYPE)[0]
     bad = int(wl.verify(expect_plain=(wl.decodes % 2 == 1)) != 0)
@@ -536,7 +621,7 @@ def run_reasm(args, dev, world, rank):
     metric = "WebSocket fused unmask + message reassembly GiB/s of bodies (device-resident)"
     pmc = pmc_traffic(kname, algo, metric)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(wl.host_sample(262144), args.cpu_threads or None, op="reasm", frames_per_segment=wl.fps)
     later = None
     if getattr(args, "cpu_defer", False):      # run_paths: timed on the CPU after every GPU path
@@ -991,15 +1076,17 @@ def run_decode(args, dev, world, rank, wl=None, path=DEFAULT_PATH):
             graph.replay()
             wl.decodes += 1
     elapsed, step_ms = timed_region(step, args.steps, world)
+    if args.dump_outputs:
+        dump_decoded(args.dump_outputs, rank, wl.buf, wl.wire_bytes, wl.desc, wl.res, wl.nseg, wl.fps)
     elapsed = D.allreduce([elapsed], op="max", device=dev)[0]      # bench contract: max over ranks
 
-    # the dominant kernel's own launch duration, live: the piece path's K2 timed by HIP
+    # --full: the dominant kernel's own launch duration, live: the piece path's K2 timed by HIP
     # events recorded around each K2 launch on the calls' stream (library option
     # k2_timing), over a second region of the same calls (events between kernels would
     # perturb the contract's region above, so it is not timed this way)
     kpath = decode_path(path, wl)
     k2_ms = None
-    if kpath == 3 and not args.graph:
+    if args.full and kpath == 3 and not args.graph:
         wl.W.set_option("k2_timing", 1)
         c0, n0 = wl.W.get_stat("k2_calls"), wl.W.get_stat("k2_ns")
         for _ in range(args.steps):
@@ -1119,6 +1206,7 @@ def run_paths(args, dev):
         a = copy.copy(args)
         a.config, a.op, a.graph, a.frames, a.fps, a.plen, a.inflight = cfg, op, False, None, None, None, 1
         a.readcache = PATH_READCACHE if op == "reasm" else 0
+        a.dump_outputs = None                # the headline's outputs only
         # CPU baselines run after every path is timed: the GPU never idles for seconds between
         # paths (a decode after idle time runs its first calls slower, DESIGN §4 "Short timed regions")
         a.cpu_defer, a.no_cpu = not args.no_cpu, True
@@ -1225,6 +1313,18 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg2")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else this benchmark measures: the CPU baselines, "
+                         "the XOR-stream reference, the dominant kernel's own launch time (a second region of "
+                         "calls), the host-buffer end-to-end run and the other single-GPU paths (`paths`); each "
+                         "can be left out again with its --no-... option. Without --full a run sets up, warms "
+                         "up, times the steps, checks the result and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left with the caller as DIR/<name>.npy "
+                         "(float32 / float64): byte sums of every chunk of the wire buffer and its bytes at "
+                         "seeded positions, the frame descriptors and the segment results (--op encode: the "
+                         "encoded wire and the frame offsets). The same arguments give the same inputs, so two "
+                         "builds can be compared file by file. Not for --op reasm or the strong-scaling configs")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: 1, the job's share (OMP_NUM_THREADS) and every CPU of the process)")
@@ -1265,6 +1365,8 @@ def main():
                          "decode + message reassembly (use with --config cfg5), or the whole batch as ONE raw "
                          "rx stream with no frame offsets (device-side boundary discovery)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.op == "reasm" or (args.op == "decode" and args.config in STRONG)):
+        ap.error("--dump-outputs: not available for --op reasm or the strong-scaling configs")
     # --gpus N means N ranks: launched here (one child process per GPU, before anything touches
     # a GPU) unless a launcher (torchrun) already set WORLD_SIZE, which must then equal N
     if "WORLD_SIZE" not in os.environ:
@@ -1321,18 +1423,18 @@ def main():
     wl = Workload.make(args.config, dev, nframes=args.frames, fps=args.fps, plen=args.plen, first_frame=rank * nfr)
     torch.cuda.synchronize()
     sample = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         sample = wl.host_sample(262144)
     from util_amd import dist as D
 
-    # a plain streaming reference on the same bytes with the same timing method: an in-place XOR
+    # --full: a plain streaming reference on the same bytes with the same timing method: an in-place XOR
     # of the wire in one-shot 256 x 4 blocks over 16 KiB pieces in the same two windows, no
     # frame logic (calibration kernel, libwsframe_amd_bench.so mode 72) — how close the decode
     # step is to moving the same bytes with nothing else to do; an even number of calls leaves
     # the buffer as it was. (Measured before the decode's warm-up; it does not warm the device
     # up for the decode — tools/exp_ramp.py, DESIGN §4 "Short timed regions".)
     xor_stream = None
-    if not args.no_xor_stream:
+    if args.full and not args.no_xor_stream:
         lib = wl.W.load_bench_lib()
         nb = wl.wire_bytes // 16 * 16
         st = torch.cuda.current_stream().cuda_stream
@@ -1353,7 +1455,7 @@ def main():
     if xor_stream is not None:
         xor_stream["step_rate_over_xor_stream"] = round(xor_stream["ms"] / out["roofline"]["step_ms_mean"], 4)
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.no_e2e:
         e2e, flips = end_to_end(wl)
         wl.decodes += flips
         e2e_mism = wl.verify(expect_plain=(wl.decodes % 2 == 1))
@@ -1374,9 +1476,9 @@ def main():
                           "GBps_per_link": round(wl.wire_bytes / dt / 1e9, 1),
                           "GBps_total": round((world - 1) * wl.wire_bytes / dt / 1e9, 1)}
         del recv
-    # every other single-GPU path of SURVEY §8, timed by the same protocol in the same run
+    # --full: every other single-GPU path of SURVEY §8, timed by the same protocol in the same run
     # (N = 1 only: the scaling points time the headline alone)
-    if world == 1 and not args.no_paths and args.config == "cfg2" and args.frames is None:
+    if world == 1 and args.full and not args.no_paths and args.config == "cfg2" and args.frames is None:
         wl.free()
         del wl
         out["paths"], m = run_paths(args, dev)

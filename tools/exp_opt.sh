@@ -6,7 +6,7 @@ for rep in 1 2; do
   for w in $1; do
     op=${w%%:*}; cfg=${w##*:}
     for o in $2; do
-      WSFRAME_AMD_OPTIONS="$o" timeout -k 10 300 python bench.py --op $op --config $cfg --no-cpu --no-e2e --inflight 1 --steps 50 2>/dev/null \
+      WSFRAME_AMD_OPTIONS="$o" timeout -k 10 300 python bench.py --full --op $op --config $cfg --no-cpu --no-e2e --inflight 1 --steps 50 2>/dev/null \
         | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$op $cfg $o', d['value'], d['ms_per_step'], d['roofline']['frac'], d['verified'])"
     done
   done
