@@ -1,38 +1,18 @@
-// ws_common.h — shared device types and the RFC 6455 header parse used by every
-// decode kernel (one definition, so the walker, the split walk kernel and the
-// fallback paths cannot drift apart).
+// ws_common.h — what the decode kernels and their launchers share: the payload stream's
+// loads and stores, the unmask round, the LDS-window walk round and the host-side launch
+// interfaces. The reactor loop's rules (header parse, per-candidate outcome, what a consumed
+// frame leaves behind) have one definition in ws_step.h, so the walker, the split walk kernel
+// and the fallback paths cannot drift apart.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <atomic>
 
-#include "../../include/wsframe_amd.h"
+#include "ws_step.h"
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// Global-address-space views: hot loops must emit global_load/store, not flat_*
-// (flat ops complete out of order, so hipcc drains vmcnt+lgkmcnt before each one
-// and every load becomes its own round trip).
-// the unmask kernel's unit (ws_piece.hip K2, also behind the raw-stream path): one-shot
-// 256-thread blocks over WS_PIECE_U KiB per wave, 2^WS_PIECE_SHIFT bytes per block
-#ifndef WS_PIECE_U
-#define WS_PIECE_U 4
-#define WS_PIECE_SHIFT 14                   // 16 KiB = 256 threads * WS_PIECE_U * 16 B
-#endif
-#define WS_GLOBAL __attribute__((address_space(1)))
-typedef WS_GLOBAL u32x4 gu32x4;
-typedef WS_GLOBAL u32 gu32;
-typedef WS_GLOBAL u64 gu64;
-typedef WS_GLOBAL unsigned char gu8;
 // Constant-address-space view: wave-uniform loads through it become s_load_*.
 typedef __attribute__((address_space(4))) const u32 cu32;
-
-template <typename T>
-__device__ __forceinline__ WS_GLOBAL T* gptr(const void* p) {
-    return reinterpret_cast<WS_GLOBAL T*>(reinterpret_cast<uintptr_t>(p));
-}
 
 // Cache policy of the payload stream (A/B-able): 0 plain, 1 nontemporal loads+stores, 2 nt stores,
 // 4 nontemporal loads + the caller's own sc1|nt buffer stores (st16<4> is an nt store).
@@ -60,63 +40,6 @@ __device__ __forceinline__ void st16_sc1nt(u32x4 v, __amdgpu_buffer_rsrc_t r, u3
                                            (int)off, 0, 18);
 }
 
-__device__ __forceinline__ u32 rotl32(u32 x, u32 r) { return r ? (x << r) | (x >> (32 - r)) : x; }
-
-// Result of parsing one frame header (websocketframe.c:112-165).
-enum { WS_PARSE_INCOMPLETE = 0, WS_PARSE_FRAME = 1, WS_PARSE_WRAP = 2 };
-struct WsHdr {
-    int kind;      // WS_PARSE_*
-    u32 b0, b1;    // header bytes 0 and 1
-    u32 hdr;       // 2 + ext + mask
-    u32 masked;    // MASK bit
-    u32 key;       // little-endian masking key (valid if masked)
-    u64 plen;      // payload length
-    int ret;       // (int) return value (:164)
-};
-
-// h0 = header bytes 0..7, h1 = bytes 8..15 (little-endian), avail = bytes left (>= 2).
-// Mirrors websocketframe.c:121-164 exactly, plus the batch fence: a MASKED frame
-// whose u64 length sum wraps and would pass the :149 check is WS_PARSE_WRAP (the
-// reference would unmask past the buffer: undefined behaviour).
-__device__ __forceinline__ WsHdr ws_parse(u64 h0, u64 h1, u64 avail) {
-    WsHdr r;
-    r.b0 = (u32)h0 & 0xFFu;
-    r.b1 = (u32)(h0 >> 8) & 0xFFu;
-    const u32 p7 = r.b1 & 0x7Fu;                                   // :129
-    r.masked = r.b1 >> 7;                                          // :126-127
-    const u32 ext = p7 < 126 ? 0u : (p7 == 126 ? 2u : 8u);         // :134-145
-    r.hdr = 2u + ext + (r.masked ? 4u : 0u);
-    r.kind = WS_PARSE_INCOMPLETE;
-    r.key = 0;
-    r.plen = 0;
-    r.ret = 0;
-    if (avail < r.hdr) return r;                                   // :131,136,142
-    if (ext == 0) r.plen = p7;
-    else if (ext == 2) r.plen = ((h0 >> 16) & 0xFFu) << 8 | ((h0 >> 24) & 0xFFu);   // memReadBE16
-    else r.plen = __builtin_bswap64((h0 >> 16) | (h1 << 48));                          // memReadBE64
-    const u64 total = (u64)r.hdr + r.plen;                         // u64, may wrap (:149)
-    if (avail < total) return r;                                   // :149-150
-    if (r.masked && total < r.plen) { r.kind = WS_PARSE_WRAP; return r; }
-    r.key = ext == 0 ? (u32)(h0 >> 16) : (ext == 2 ? (u32)(h0 >> 32) : (u32)(h1 >> 16));
-    r.ret = (int)(u32)total;                                       // :164, truncating
-    r.kind = WS_PARSE_FRAME;
-    return r;
-}
-
-// Header bytes [p, p+16) from the 32 bytes x0|x1 loaded at floor16(p), o = p & 15,
-// as two little-endian u64 (bytes 0..7, 8..15). Branch-free on purpose: a divergent
-// per-lane dword select around these loads produced nondeterministic header reads
-// under load on ROCm 7.2.
-__device__ __forceinline__ void ws_hdr_from32(const u32x4 x0, const u32x4 x1, u32 o, u64& h0, u64& h1) {
-    const u64 w0 = (u64)x0.x | ((u64)x0.y << 32), w1 = (u64)x0.z | ((u64)x0.w << 32);
-    const u64 w2 = (u64)x1.x | ((u64)x1.y << 32), w3 = (u64)x1.z | ((u64)x1.w << 32);
-    const u32 sh = 8u * (o & 7);
-    const bool up = o >= 8;
-    const u64 a0 = up ? w1 : w0, a1 = up ? w2 : w1, a2 = up ? w3 : w2;
-    h0 = sh ? (a0 >> sh) | (a1 << (64 - sh)) : a0;
-    h1 = sh ? (a1 >> sh) | (a2 << (64 - sh)) : a1;
-}
-
 // The wire length of the batch's first frame (of the first segment with >= 2 bytes among the
 // first 8), 0 unless it is a plain complete frame: K1's first-step stride guess for the next
 // call on the stream (ws_piece.hip; a wrong guess costs loads only). One thread.
@@ -125,26 +48,9 @@ __device__ __forceinline__ u32 ws_first_frame_len(const unsigned char* buf, cons
     for (u32 s = 0; s < nseg && s < 8; ++s) {
         const u64 so = seg_off[s], sl = seg_len[s];
         if (sl < 2) continue;
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(buf + so);
-        const WS_GLOBAL u32x4* q = reinterpret_cast<const WS_GLOBAL u32x4*>(pa & ~(uintptr_t)15);
-        u64 h0, h1;
-        ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-        const WsHdr h = ws_parse(h0, h1, sl);
-        return h.kind == WS_PARSE_FRAME && h.ret > 1 && (u64)h.hdr + h.plen == (u64)(u32)h.ret ? (u32)h.ret : 0u;
+        return ws_plain_frame_len(ws_load_hdr(reinterpret_cast<uintptr_t>(buf + so), sl));
     }
     return 0;
-}
-
-// Descriptor as two 16-B stores (WebsocketFrameDesc_t layout).
-__device__ __forceinline__ void ws_store_desc(WebsocketFrameDesc_t* d, u64 frame_off, const WsHdr& h) {
-    const u64 dof = h.plen ? frame_off + h.hdr : WEBSOCKET_DATA_OFF_NULL;
-    u32x4 q0, q1;
-    q0.x = (u32)frame_off; q0.y = (u32)(frame_off >> 32); q0.z = (u32)dof; q0.w = (u32)(dof >> 32);
-    q1.x = (u32)h.plen; q1.y = (u32)(h.plen >> 32); q1.z = (u32)h.ret;
-    q1.w = (h.b0 >> 7) | ((h.b0 & 0x0Fu) << 8) | (h.masked << 16) | (h.hdr << 24);
-    gu32x4* g = gptr<u32x4>(d);
-    g[0] = q0;
-    g[1] = q1;
 }
 
 __device__ __forceinline__ void ws_store_res(WebsocketSegResult_t* res, u64 consumed, u32 nf, int status) {
@@ -306,13 +212,8 @@ struct WsRound {
 
 __device__ __forceinline__ WsRound ws_lds_round(const u32x4* win, u64 W0, u64 W1, u64 lead, u64 sl, u64 off,
                                                 u64& g, u32 nf, u32 max_frames, u32 lane) {
-    if (g == 0 && off + lead < W1 && off < sl) {                       // stride seed
-        const u32 o = (u32)(off + lead - W0);
-        u64 h0, h1;
-        ws_hdr_from32(win[o >> 4], win[(o >> 4) + 1], o & 15u, h0, h1);
-        const WsHdr h = ws_parse(h0, h1, sl - off);
-        if (h.kind == WS_PARSE_FRAME && h.ret > 0) g = (u32)h.ret;
-    }
+    if (g == 0 && off + lead < W1 && off < sl)                         // stride seed
+        g = ws_plain_frame_len(ws_load_hdr_win(win, (u32)(off + lead - W0), sl - off));
     WsRound r;
     r.pos = off + (u64)lane * g;
     const bool cand = lane == 0 || g > 0;
@@ -320,17 +221,17 @@ __device__ __forceinline__ WsRound ws_lds_round(const u32x4* win, u64 W0, u64 W1
     const bool inwin = X < W1;
     const bool eval = cand && r.pos < sl && inwin;
     const u32 o = eval ? (u32)(X - W0) : 0u;
-    u64 h0, h1;
-    ws_hdr_from32(win[o >> 4], win[(o >> 4) + 1], o & 15u, h0, h1);
-    r.h = ws_parse(h0, h1, eval ? sl - r.pos : 0);
+    r.h = ws_load_hdr_win(win, o, eval ? sl - r.pos : 0);
     u32 code = 3;
     int st = WEBSOCKET_SEG_OK;
+    // ws_cand_code's cascade with the window stop (code 4) after the max_frames check, written out:
+    // calling the shared rule and overriding its result costs ws_segfuse_kernel two SGPRs (99 ->
+    // 101) and with them its eighth wave per SIMD
     if (cand) {
         if (r.pos >= sl) code = 3;
         else if (nf + lane >= max_frames) { code = 3; st = WEBSOCKET_SEG_MAX_FRAMES; }
         else if (!inwin) code = 4;
-        else if (sl - r.pos < 2) code = 3;                                 // websocketframe.c:121
-        else if (r.h.kind == WS_PARSE_INCOMPLETE) code = 3;
+        else if (r.h.kind == WS_PARSE_INCOMPLETE) code = 3;                // (fewer than 2 bytes left included)
         else if (r.h.kind == WS_PARSE_WRAP) { code = 3; st = WEBSOCKET_SEG_ERR_LEN_WRAP; }
         else if (r.h.ret <= 0) { code = 2; st = r.h.ret < 0 ? WEBSOCKET_SEG_ERR_DECODE : WEBSOCKET_SEG_OK; }
         else code = (u64)(u32)r.h.ret == g ? 0u : 1u;

@@ -37,28 +37,6 @@
 static_assert((1 << PIECE_SHIFT) == PIECE_T * PIECE_U * 16, "piece = one block's chunks");
 #define PIECE_NONE 0xFFFFFFFFFFFFFFFFull
 
-// item: w0 = P0 | rkey[15:0] << 48, w1 = P1 | rkey[31:16] << 48 (origin-relative bytes < 2^48)
-__device__ __forceinline__ void put_item(gu32x4* it, u64 p0, u64 p1, u32 rk) {
-    const u64 w0 = p0 | ((u64)(rk & 0xFFFFu) << 48), w1 = p1 | ((u64)(rk >> 16) << 48);
-    u32x4 q;
-    q.x = (u32)w0; q.y = (u32)(w0 >> 32); q.z = (u32)w1; q.w = (u32)(w1 >> 32);
-    *it = q;
-}
-
-// pieces whose first byte is in [lo, hi) (origin-relative) get s << 32 | k; only pieces of the
-// batch's table [pbase, pend) exist (a segment outside [lo, hi) of the call marks the batch
-// unordered, and its pointers are clipped here). start, stride: the lanes of a group write one
-// range together, lane j the pieces j, j + stride, ...
-__device__ __forceinline__ u64 first_piece(u64 lo, u64 pbase) {
-    const u64 p = (lo + (1ull << PIECE_SHIFT) - 1) >> PIECE_SHIFT;
-    return p > pbase ? p : pbase;
-}
-__device__ __forceinline__ void put_ptrs(u64* ptr, u64 pbase, u64 pend, u64 lo, u64 hi, u32 s, u32 k, u64 start = 0,
-                                         u64 stride = 1) {
-    for (u64 p = first_piece(lo, pbase) + start; (p << PIECE_SHIFT) < hi && p < pend; p += stride)
-        *gptr<u64>(ptr + (p - pbase)) = ((u64)s << 32) | k;
-}
-
 // What one segment walk needs (K1).
 struct WalkArgs {
     const unsigned char* buf;
@@ -108,7 +86,12 @@ __device__ __forceinline__ void walk_group(const WalkArgs& A, u32 s, bool active
     const u64 ibase = (u64)sc * A.max_frames;
     const u64 sorg = so + lead0;
     const uintptr_t seg = reinterpret_cast<uintptr_t>(A.buf + so);
-    if ((ST & 4) && active) put_ptrs(A.ptr, A.pbase, pend, sc ? prev_end + lead0 : 0, sorg, sc, 0, gl, G);
+    // piece pointers of this segment: sc << 32 | item, within the batch's table [pbase, pend) (a
+    // segment outside [lo, hi) of the call marks the batch unordered, and its pointers are clipped)
+    auto put_ptrs = [&](u64 lo, u64 hi, u32 k, u64 start = 0, u64 stride = 1) {
+        ws_put_ptrs(A.ptr, A.pbase, pend, lo, hi, ((u64)sc << 32) | k, start, stride);
+    };
+    if ((ST & 4) && active) put_ptrs(sc ? prev_end + lead0 : 0, sorg, 0, gl, G);
     // g0: the stride guess of the first step (the host's hint, 0 = none): lane k parses off + k*g0
     // at once; lane 0's frame is always the true first one, so a wrong guess costs nothing but
     // its loads (code 1 at lane 0 takes the true length)
@@ -164,26 +147,11 @@ __device__ __forceinline__ void walk_group(const WalkArgs& A, u32 s, bool active
             }
         }
         const bool eval = cand && pos < sl;
-        const uintptr_t pa = seg + (eval ? pos : 0);
-        const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-        const u32x4 x0 = q[0], x1 = q[1];                                  // WEBSOCKET_BATCH_PAD: readable
-        u64 h0, h1;
-        ws_hdr_from32(x0, x1, (u32)(pa & 15), h0, h1);
-        const WsHdr h = ws_parse(h0, h1, eval ? sl - pos : 0);
-        // per-lane outcome in the reactor loop's order (net_reactor.c:515-526):
-        //   0 consumed, chain continues   1 consumed, length != g: step ends (stride lanes)
-        //   2 consumed, walk ends (ret <= 0)   3 not consumed, walk ends
+        const WsHdr h = ws_load_hdr(seg + (eval ? pos : 0), eval ? sl - pos : 0);
+        // per-lane outcome in the reactor loop's order (ws_cand_code; alphabet lanes take any length)
         u32 code = 3;
         int st = WEBSOCKET_SEG_OK;
-        if (cand) {
-            if (pos >= sl) code = 3;
-            else if (nf + depth >= A.max_frames) { code = 3; st = WEBSOCKET_SEG_MAX_FRAMES; }
-            else if (sl - pos < 2) code = 3;                                 // websocketframe.c:121
-            else if (h.kind == WS_PARSE_INCOMPLETE) code = 3;
-            else if (h.kind == WS_PARSE_WRAP) { code = 3; st = WEBSOCKET_SEG_ERR_LEN_WRAP; }
-            else if (h.ret <= 0) { code = 2; st = h.ret < 0 ? WEBSOCKET_SEG_ERR_DECODE : WEBSOCKET_SEG_OK; }
-            else code = alpha || (u64)(u32)h.ret == g ? 0u : 1u;
-        }
+        if (cand) code = ws_cand_code(pos, sl, nf + depth, A.max_frames, h, g, alpha, st);
         // the chain: mm = frames before the stopping one (G: none stops), the stopping lane's code,
         // and (alpha) the chain's lanes by depth
         u32 mm, code_m, lm = 0;
@@ -220,20 +188,18 @@ __device__ __forceinline__ void walk_group(const WalkArgs& A, u32 s, bool active
         const u64 fo = sorg + pos;
         const u64 p0 = fo + h.hdr, fe = p0 + h.plen;
         if (mine) {                                                         // consumed frames, in parallel
-            if (ST & 2)
-                put_item(gptr<u32x4>(A.items + ibase + nf + depth), p0, h.masked ? fe : p0,
-                         rotl32(h.key, 8u * (u32)(p0 & 3)));
+            if (ST & 2) *gptr<u32x4>(A.items + ibase + nf + depth) = ws_frame_item(h, fo);
             if ((ST & 1) && h.ret != 0) ws_store_desc(A.desc + dbase + nf + depth, so + pos, h);
         }
         // the pieces whose first byte lies in a consumed frame point at it: a lane writes its frame's
         // first WALK_PTR_OWN pieces; a longer frame's rest the group's 16 lanes write together
         // (one lane alone would take milliseconds over a multi-GiB frame)
-        const u64 pf = first_piece(fo, A.pbase);
+        const u64 pf = ws_first_piece(fo, A.pbase);
         const u64 phi = (fe + (1ull << PIECE_SHIFT) - 1) >> PIECE_SHIFT;   // pieces [pf, phi) start in [fo, fe)
         const u64 pl = phi < pend ? phi : pend;
         if ((ST & 4) && mine) {
             const u64 hown = pf + WALK_PTR_OWN < pl ? (pf + WALK_PTR_OWN) << PIECE_SHIFT : fe;
-            put_ptrs(A.ptr, A.pbase, pend, fo, hown, sc, nf + depth);
+            put_ptrs(fo, hown, nf + depth);
         }
         bool pending = (ST & 4) && mine && pf + WALK_PTR_OWN < pl;
         while (__ballot(pending)) {
@@ -243,7 +209,7 @@ __device__ __forceinline__ void walk_group(const WalkArgs& A, u32 s, bool active
             const u64 a = __shfl(fo, (int)src), b = __shfl(fe, (int)src);
             const u32 kk = nf + (u32)__shfl((int)depth, (int)src);
             if (gl == li) pending = false;
-            if (gm) put_ptrs(A.ptr, A.pbase, pend, a, b, sc, kk, WALK_PTR_OWN + gl, WALK_G);
+            if (gm) put_ptrs(a, b, kk, WALK_PTR_OWN + gl, WALK_G);
         }
         // the last consumed frame's lane: the stopping lane if it consumed, else the one before it
         const u32 llast = (code_m == 1 || code_m == 2 || mm == G) ? lm
@@ -296,15 +262,15 @@ __device__ __forceinline__ void walk_group(const WalkArgs& A, u32 s, bool active
         // segment
         if (ST & 4) {
             const u32 cnt = nf + extra;
-            put_ptrs(A.ptr, A.pbase, pend, walked_end, sorg + sl, sc, cnt, gl, G);
-            if (sc == A.nseg - 1) put_ptrs(A.ptr, A.pbase, pend, sorg + sl, A.hi + lead0, 0xFFFFFFFFu, 0xFFFFFFFFu, gl, G);
+            put_ptrs(walked_end, sorg + sl, cnt, gl, G);
+            if (sc == A.nseg - 1) ws_put_ptrs(A.ptr, A.pbase, pend, sorg + sl, A.hi + lead0, PIECE_NONE, gl, G);
         }
         if (!(ST & 8) && gl == 0 && nf + extra == 0xFFFFFFFFu) *gptr<u32>(A.nwork) = off;   // keeps the walk live
         if ((ST & 8) && gl == 0) {
             const u32 cnt = nf + extra;
             ws_store_res(A.res + sc, off, nf, status);
             *gptr<u32>(A.nwork + sc) = cnt;
-            put_item(gptr<u32x4>(reinterpret_cast<u32x4*>(A.segr + sc)), sorg, sorg + sl, cnt);   // WsSegRec
+            *gptr<u32x4>(A.segr + sc) = ws_item_pack(sorg, sorg + sl, cnt);                      // WsSegRec
             cnt_out = cnt;
             nonu_out = nonu;
         }
@@ -404,9 +370,7 @@ __global__ __launch_bounds__(PIECE_T) void ws_piece_unmask_kernel(unsigned char*
         if (SR) {
             const u32x4 R = *reinterpret_cast<const __attribute__((address_space(4))) u32x4*>(
                 reinterpret_cast<uintptr_t>(segr + s));
-            const u64 w0 = (u64)R.x | ((u64)R.y << 32), w1 = (u64)R.z | ((u64)R.w << 32);
-            slo = w0 & 0xFFFFFFFFFFFFull; shi = w1 & 0xFFFFFFFFFFFFull;
-            cnt = (u32)(w0 >> 48) | ((u32)(w1 >> 48) << 16);
+            ws_item_unpack(R, slo, shi, cnt);
         } else {
             // (the raw-stream path) the three loads issued together: the compiler would otherwise sink
             // the second and third below the `slo >= r1` exit, three dependent round trips per wave
@@ -437,9 +401,9 @@ __global__ __launch_bounds__(PIECE_T) void ws_piece_unmask_kernel(unsigned char*
             const bool valid = j < cnt && lane < step;
             u32x4 q = {0, 0, 0, 0};
             if (valid) q = items[(u64)s * max_frames + j];
-            const u64 w0 = (u64)q.x | ((u64)q.y << 32), w1 = (u64)q.z | ((u64)q.w << 32);
-            const u64 P0 = w0 & 0xFFFFFFFFFFFFull, P1 = w1 & 0xFFFFFFFFFFFFull;
-            const u32 rk = (u32)(w0 >> 48) | ((u32)(w1 >> 48) << 16);
+            u64 P0, P1;
+            u32 rk;
+            ws_item_unpack(q, P0, P1, rk);
             // items are in address order: the first one starting at/after r1 ends the scan
             const u64 past = __ballot(valid && P0 >= r1);
             const u32 nlim = past ? (u32)__builtin_ctzll(past) : 64u;

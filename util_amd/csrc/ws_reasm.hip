@@ -121,8 +121,9 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
             cstop_frame = (int)(k0 + cst);
         }
         if (gl < ntake) {
-            const u64 p0 = ((u64)it.x | ((u64)it.y << 32)) & 0xFFFFFFFFFFFFull;
-            const u32 rk = (u32)(((u64)it.x | ((u64)it.y << 32)) >> 48) | ((u32)(((u64)it.z | ((u64)it.w << 32)) >> 48) << 16);
+            u64 p0, p1;
+            u32 rk;
+            ws_item_unpack(it, p0, p1, rk);
             const u32 sh = 8u * (u32)(p0 & 3);
             const u32 key = sh ? (rk >> sh) | (rk << (32 - sh)) : rk;       // the frame's key (wire order)
             const u64 dst = ob + qs + lead_o;
@@ -494,8 +495,8 @@ __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8)
                 // body bi-1's bytes as they sit at chunk positions 0..15, body bi's first 16 bytes
                 const u32 op = (u32)(px0 + (C0 - obase - pdst) - W0), oc = (u32)(b.x0 - W0);
                 u64 p0, p1, c0, c1;
-                ws_hdr_from32(win[op >> 4], win[(op >> 4) + 1], op & 15u, p0, p1);
-                ws_hdr_from32(win[oc >> 4], win[(oc >> 4) + 1], oc & 15u, c0, c1);
+                ws_load16_win(win, op, p0, p1);
+                ws_load16_win(win, oc, c0, c1);
                 // shift body bi's bytes up by sb positions (128-bit left shift by 8*sb bits)
                 const u32 sh = 8u * sb;
                 const u64 n0 = sh < 64 ? c0 << sh : 0ull;

@@ -23,48 +23,23 @@
 #include "ws_common.h"
 
 #define SPASS_T 256
-#define PIECE_SHIFT_S WS_PIECE_SHIFT
 
-// outcome bits packed with the candidate index: k << 36 | code << 34 | stf << 32 | (u32)ret
-//   code 1: consumed, length != g   2: consumed, walk ends (ret <= 0)   3: not consumed
-//   stf (code 3): 0 OK, 1 MAX_FRAMES, 2 LEN_WRAP; (code 2): 0 ret == 0, 1 ret < 0
+// outcome bits packed with the candidate index: k << 36 | code << 34 | status bits << 32 | (u32)ret
+// (ws_cand_code's code, never 0, and ws_status_bits of its status)
 __device__ __forceinline__ void stream_pass_one(const unsigned char* __restrict__ buf, u64 len, u64 P, u64 g, u32 nf,
                                                 u32 max_frames, u64 k, WebsocketFrameDesc_t* __restrict__ desc,
                                                 u32x4* __restrict__ items, u64* __restrict__ ptr, u64 pend,
                                                 unsigned long long* __restrict__ stop) {
     const u64 lead0 = reinterpret_cast<uintptr_t>(buf) & 15;
-    const u64 pos = P + k * g;
-    u32 code = 0, stf = 0;
-    WsHdr h = {};
-    if (pos >= len) code = 3;
-    else if ((u64)nf + k >= max_frames) { code = 3; stf = 1; }
-    else if (len - pos < 2) code = 3;                                        // websocketframe.c:121
-    else {
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(buf + pos);
-        const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-        u64 h0, h1;
-        ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-        h = ws_parse(h0, h1, len - pos);
-        if (h.kind == WS_PARSE_INCOMPLETE) code = 3;
-        else if (h.kind == WS_PARSE_WRAP) { code = 3; stf = 2; }
-        else if (h.ret <= 0) { code = 2; stf = h.ret < 0 ? 1u : 0u; }
-        else code = (u64)(u32)h.ret == g ? 0u : 1u;
-    }
-    if (code == 0 || code == 1 || code == 2) {                               // speculative writes
-        const u64 fo = lead0 + pos, p0 = fo + h.hdr, fe = p0 + h.plen;
-        const u64 slot = (u64)nf + k;
-        const u64 w0 = p0 | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) & 0xFFFFu) << 48);
-        const u64 w1 = (h.masked ? fe : p0) | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) >> 16) << 48);
-        u32x4 it;
-        it.x = (u32)w0; it.y = (u32)(w0 >> 32); it.z = (u32)w1; it.w = (u32)(w1 >> 32);
-        *gptr<u32x4>(items + slot) = it;
-        for (u64 p = (fo + (1ull << PIECE_SHIFT_S) - 1) >> PIECE_SHIFT_S; (p << PIECE_SHIFT_S) < fe && p < pend; ++p)
-            *gptr<u64>(ptr + p) = slot;                                      // segment 0, item `slot`
-        if (h.ret != 0) ws_store_desc(desc + slot, pos, h);
-    }
+    const u64 pos = P + k * g, slot = (u64)nf + k;
+    const bool eval = pos < len;
+    const WsHdr h = ws_load_hdr(reinterpret_cast<uintptr_t>(buf) + (eval ? pos : 0), eval ? len - pos : 0);
+    int st;
+    const u32 code = ws_cand_code(pos, len, slot, max_frames, h, g, false, st);
+    if (code != 3) ws_emit_frame(h, pos, lead0, slot, desc, items, ptr, pend);   // speculative writes
     if (code != 0) {
         const unsigned long long word = ((unsigned long long)k << 36) | ((unsigned long long)code << 34) |
-                                        ((unsigned long long)stf << 32) | (u32)h.ret;
+                                        ((unsigned long long)ws_status_bits(st) << 32) | (u32)h.ret;
         atomicMax(stop, ~word);                                              // the first stop, inverted
     }
 }
@@ -106,15 +81,7 @@ __global__ void ws_stream_init_kernel(SdState* __restrict__ sd) {
 // positive return: then only candidate 0 exists), and the candidate count of a pass
 __device__ __forceinline__ void sd_stride(const unsigned char* __restrict__ buf, u64 len, u64 P, u32 nf,
                                           u32 max_frames, u64& g, u64& K) {
-    g = 0;
-    if (P < len && len - P >= 2) {
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(buf + P);
-        const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-        u64 h0, h1;
-        ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-        const WsHdr h = ws_parse(h0, h1, len - P);
-        if (h.kind == WS_PARSE_FRAME && h.ret > 0) g = (u32)h.ret;
-    }
+    g = P < len ? ws_plain_frame_len(ws_load_hdr(reinterpret_cast<uintptr_t>(buf + P), len - P)) : 0;
     u64 kf = g ? (len - P) / g + 1 : 1;
     if (kf > (u64)max_frames - nf + 1) kf = (u64)max_frames - nf + 1;
     K = kf < SD_KMAX ? kf : SD_KMAX;
@@ -182,38 +149,20 @@ __device__ __forceinline__ SwOut stream_walk(const unsigned char* __restrict__ b
         const u64 pos = off + (u64)lane * g;
         const bool cand = lane < wl;
         const bool eval = cand && pos < len;
-        const uintptr_t pa = seg + (eval ? pos : 0);
-        const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-        u64 h0, h1;
-        ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-        const WsHdr h = ws_parse(h0, h1, eval ? len - pos : 0);
+        const WsHdr h = ws_load_hdr(seg + (eval ? pos : 0), eval ? len - pos : 0);
         u32 code = 3, bnd = 0;
         int st = WEBSOCKET_SEG_OK;
         if (cand) {
-            if (pos >= len) code = 3;
-            else if (pos >= end) { code = 3; bnd = 1; }                      // the next wavefront's frame
-            else if (nf + lane >= max_frames) { code = 3; st = WEBSOCKET_SEG_MAX_FRAMES; }
-            else if (len - pos < 2) code = 3;                                // websocketframe.c:121
-            else if (h.kind == WS_PARSE_INCOMPLETE) code = 3;
-            else if (h.kind == WS_PARSE_WRAP) { code = 3; st = WEBSOCKET_SEG_ERR_LEN_WRAP; }
-            else if (h.ret <= 0) { code = 2; st = h.ret < 0 ? WEBSOCKET_SEG_ERR_DECODE : WEBSOCKET_SEG_OK; }
-            else code = (u64)(u32)h.ret == g ? 0u : 1u;
+            code = ws_cand_code(pos, len, nf + lane, max_frames, h, g, false, st);
+            // a frame at or past `end` is the next wavefront's, whatever it is
+            if (pos < len && pos >= end) { code = 3; st = WEBSOCKET_SEG_OK; bnd = 1; }
         }
         const u64 stopm = __ballot(cand && code != 0);
         const u32 mm = stopm ? (u32)__builtin_ctzll(stopm) : wl;
         const u32 code_m = stopm ? (u32)__builtin_amdgcn_readlane((int)code, (int)mm) : 0u;
         const u32 ntake = mm + ((code_m == 1 || code_m == 2) ? 1u : 0u);
-        const u64 fo = lead0 + pos, p0 = fo + h.hdr, fe = p0 + h.plen;
-        if (lane < ntake) {
-            const u64 w0 = p0 | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) & 0xFFFFu) << 48);
-            const u64 w1 = (h.masked ? fe : p0) | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) >> 16) << 48);
-            u32x4 it;
-            it.x = (u32)w0; it.y = (u32)(w0 >> 32); it.z = (u32)w1; it.w = (u32)(w1 >> 32);
-            *gptr<u32x4>(items + nf + lane) = it;
-            for (u64 p = (fo + (1ull << PIECE_SHIFT_S) - 1) >> PIECE_SHIFT_S; (p << PIECE_SHIFT_S) < fe && p < pend; ++p)
-                *gptr<u64>(ptr + p) = nf + lane;
-            if (h.ret != 0) ws_store_desc(desc + nf + lane, pos, h);
-        }
+        u64 fe = 0;
+        if (lane < ntake) fe = ws_emit_frame(h, pos, lead0, nf + lane, desc, items, ptr, pend);
         if (ntake) walked_end = __shfl(fe, (int)ntake - 1);
         if (want_max && lane < ntake && h.ret > 0 && (u32)h.ret > mx) mx = (u32)h.ret;
         if (!stopm) {                                                        // every evaluated lane confirmed
@@ -265,9 +214,7 @@ __device__ __forceinline__ SwOut stream_walk(const unsigned char* __restrict__ b
     }
     if (!last && (at_bnd || !out)) return r;
     const u32 cnt = nf + extra;
-    for (u64 p = ((walked_end + (1ull << PIECE_SHIFT_S) - 1) >> PIECE_SHIFT_S) + lane;
-         (p << PIECE_SHIFT_S) < lead0 + len && p < pend; p += 64)
-        ptr[p] = cnt;
+    ws_put_ptrs(ptr, 0, pend, walked_end, lead0 + len, cnt, lane, 64);
     if (lane == 0) {
         nwork[0] = cnt;
         ws_store_res(res, off, nf, status);
@@ -330,8 +277,9 @@ __global__ __launch_bounds__(SPASS_T) void ws_stream_resolve_kernel(const unsign
     __syncthreads();
     if (word != ~0ull) {
         const u64 m = word >> 36;
-        const u32 code = (u32)(word >> 34) & 3u, stf = (u32)(word >> 32) & 3u;
+        const u32 code = (u32)(word >> 34) & 3u;
         const int ret = (int)(u32)word;
+        status = ws_bits_status((u32)(word >> 32) & 3u);                    // (code 1: OK)
         const u64 pos_m = P + m * g;
         const u64 slot_m = (u64)nf + m;
         nf2 = nf + (u32)m;
@@ -348,31 +296,23 @@ __global__ __launch_bounds__(SPASS_T) void ws_stream_resolve_kernel(const unsign
                 if (m < 64 && ++short_passes >= 2) phase = SD_WALK;
             }
         } else if (code == 2) {                                              // ret <= 0: unmasked, walk ends
-            if (ret != 0) { nf2 += 1; status = WEBSOCKET_SEG_ERR_DECODE; }
+            if (ret != 0) nf2 += 1;                                          // ret < 0 keeps its descriptor
             else extra = 1;
             // its payload extent: the header at pos_m again (the buffer is not written yet)
-            const uintptr_t pa = reinterpret_cast<uintptr_t>(buf + pos_m);
-            const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-            u64 h0, h1;
-            ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-            const WsHdr h = ws_parse(h0, h1, len - pos_m);
+            const WsHdr h = ws_load_hdr(reinterpret_cast<uintptr_t>(buf + pos_m), len - pos_m);
             const u64 p1 = lead0 + pos_m + h.hdr + (h.masked ? h.plen : 0);
             if (threadIdx.x == 0) {
                 f_lo[0] = lead0 + pos_m; f_hi[0] = p1; f_val[0] = slot_m;
                 f_lo[1] = p1; f_hi[1] = lead0 + len; f_val[1] = (u64)nf2 + extra;
             }
         } else {
-            status = stf == 1 ? WEBSOCKET_SEG_MAX_FRAMES : (stf == 2 ? WEBSOCKET_SEG_ERR_LEN_WRAP : WEBSOCKET_SEG_OK);
             if (threadIdx.x == 0) { f_lo[0] = lead0 + pos_m; f_hi[0] = lead0 + len; f_val[0] = nf2; }
         }
     }
     __syncthreads();
     const u64 t0 = (u64)blockIdx.x * SPASS_T + threadIdx.x, ts = (u64)gridDim.x * SPASS_T;
 #pragma unroll
-    for (int f = 0; f < 2; ++f)
-        for (u64 p = ((f_lo[f] + (1ull << PIECE_SHIFT_S) - 1) >> PIECE_SHIFT_S) + t0; (p << PIECE_SHIFT_S) < f_hi[f] && p < pend;
-             p += ts)
-            ptr[p] = f_val[f];
+    for (int f = 0; f < 2; ++f) ws_put_ptrs(ptr, 0, pend, f_lo[f], f_hi[f], f_val[f], t0, ts);
     __syncthreads();
     if (threadIdx.x == 0) s_last = atomicAdd(&sd->ticket, 1u) == gridDim.x - 1;
     __syncthreads();
@@ -595,14 +535,12 @@ __device__ __forceinline__ bool rw_plausible(u32 b0, u32 b1, u32 b23, bool need_
 // 2 implausible header (a wrong start)
 __device__ __forceinline__ u32 rw_step(uintptr_t origin, u64 len, u64& pos, bool need_mask) {
     if (pos >= len || len - pos < 2) return 1;                               // websocketframe.c:121
-    const uintptr_t pa = origin + pos;
-    const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
     u64 h0, h1;
-    ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
+    ws_load16(origin + pos, h0, h1);
     if (!rw_plausible((u32)h0 & 0xFFu, (u32)(h0 >> 8) & 0xFFu, (u32)(h0 >> 16) & 0xFFFFu, need_mask)) return 2;
-    const WsHdr h = ws_parse(h0, h1, len - pos);
-    if (h.kind != WS_PARSE_FRAME || h.ret <= 0) return 1;
-    pos += (u32)h.ret;
+    const u32 fl = ws_plain_frame_len(ws_parse(h0, h1, len - pos));
+    if (!fl) return 1;
+    pos += fl;
     return 0;
 }
 
@@ -859,22 +797,9 @@ __global__ __launch_bounds__(64) void ws_rw_emit_kernel(const unsigned char* __r
     const uintptr_t origin = reinterpret_cast<uintptr_t>(buf);
     for (u64 i = lane; i < n_par; i += 64) {
         const u64 pos = cs0 + sl[i];
-        const uintptr_t pa = origin + pos;
-        const gu32x4* q = reinterpret_cast<const gu32x4*>(pa & ~(uintptr_t)15);
-        u64 h0, h1;
-        ws_hdr_from32(q[0], q[1], (u32)(pa & 15), h0, h1);
-        const WsHdr h = ws_parse(h0, h1, len - pos);                         // a frame (the owner walked it)
+        const WsHdr h = ws_load_hdr(origin + pos, len - pos);                // a frame (the owner walked it: ret > 0)
         if ((u32)h.ret > mx) mx = (u32)h.ret;
-        const u64 slot = nf0 + cnt_w + i;
-        const u64 fo = lead0 + pos, p0 = fo + h.hdr, fe = p0 + h.plen;
-        const u64 w0 = p0 | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) & 0xFFFFu) << 48);
-        const u64 w1 = (h.masked ? fe : p0) | ((u64)(rotl32(h.key, 8u * (u32)(p0 & 3)) >> 16) << 48);
-        u32x4 it;
-        it.x = (u32)w0; it.y = (u32)(w0 >> 32); it.z = (u32)w1; it.w = (u32)(w1 >> 32);
-        *gptr<u32x4>(items + slot) = it;
-        for (u64 p = (fo + (1ull << PIECE_SHIFT_S) - 1) >> PIECE_SHIFT_S; (p << PIECE_SHIFT_S) < fe && p < pend; ++p)
-            *gptr<u64>(ptr + p) = slot;
-        ws_store_desc(desc + slot, pos, h);
+        ws_emit_frame(h, pos, lead0, nf0 + cnt_w + i, desc, items, ptr, pend);
     }
     const u64 nb = ow.cs & 0x7FFFFFFFu;
     const u64 staged = nb < stgn ? nb : stgn;
@@ -1748,7 +1673,7 @@ std::atomic<unsigned long long> ws_stat_stream_splits{0};   // raw-stream calls 
 static int rw_unmask(const WsLaunch& L, const PieceWs& Pw, u32 gen, const RwSplit* sp, const RwPlan* plan) {
     if (!sp || !sp->ncut) return ws_launch_piece_unmask(L, Pw, gen);
     ++ws_stat_stream_splits;
-    const u64 cpp = 1ull << (PIECE_SHIFT_S - 4);                             // 16-B chunks per piece
+    const u64 cpp = 1ull << (WS_PIECE_SHIFT - 4);                             // 16-B chunks per piece
     for (u32 k = 0; k <= sp->ncut; ++k) {
         const u64 a = k ? sp->p[k - 1] : 0, b = k < sp->ncut ? sp->p[k] : Pw.npieces;
         if (k) {
@@ -1819,7 +1744,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     // the piece-path views of the workspace
     {
         const u64 lead0 = reinterpret_cast<uintptr_t>(d_buf) & 15;
-        Pw.npieces = len + lead0 ? ((len + lead0 - 1) >> PIECE_SHIFT_S) + 1 : 0;
+        Pw.npieces = len + lead0 ? ((len + lead0 - 1) >> WS_PIECE_SHIFT) + 1 : 0;
         Pw.pbase = 0;
         Pw.c_lo = 0;
         Pw.c_hi = (len + lead0 + 15) >> 4;
@@ -1872,7 +1797,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
                 const u64 p1 = Pw.npieces * (u64)spl2 / 256;
                 if (p1 > SP.p[0] && p1 < Pw.npieces) SP.p[SP.ncut++] = p1;
             }
-            for (u32 k = 0; k < SP.ncut; ++k) SP.x[k] = (SP.p[k] << PIECE_SHIFT_S) - lead0;
+            for (u32 k = 0; k < SP.ncut; ++k) SP.x[k] = (SP.p[k] << WS_PIECE_SHIFT) - lead0;
             SP.wait = sw >= 0 && sw <= 2 ? sw : 0;
             SP.shift[0] = c0 >= 0 && c0 <= 6 ? (u32)c0 : 2u;
             SP.shift[1] = c1 >= 0 && c1 <= 6 ? (u32)c1 : 1u;
