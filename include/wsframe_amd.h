@@ -26,6 +26,11 @@ extern "C" {
 #endif
 
 #define WSFRAME_AMD_EXPORT __attribute__((visibility("default")))
+/* Entry points of libwsframe_amd_ctl.so only: that library is libwsframe_amd.so (every symbol
+ * above and below, same objects) plus the control-direct entry points marked with this macro;
+ * link it instead of libwsframe_amd.so to use them. libwsframe_amd.so's own symbol table stays
+ * the reference's eight symbols and the batch API. */
+#define WSFRAME_AMD_CTL_EXPORT __attribute__((visibility("default")))
 
 /* ---- Part 1: reference ABI (websocketframe.h:10-19, :42-49) ---------------- */
 
@@ -318,6 +323,50 @@ WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(const unsigned char
                                                              WebsocketMsgDesc_t* d_msg, unsigned int* d_nmsg,
                                                              unsigned char* d_open, unsigned int readcache_max_size,
                                                              unsigned int* d_cached, void* hip_stream);
+
+/* The same with delivery flags: flags == 0 is websocketframeBatchReassembleDeviceEx bit for
+ * bit; an unknown flag bit returns a negative code (websocketframeGpuLastError) and launches
+ * nothing.
+ *
+ * WEBSOCKET_REASM_CONTROL_DIRECT: control frames (PING, PONG, CLOSE: a consumed frame with
+ * type & 8, decided on the opcode alone) are delivered apart from fragmented messages, as
+ * RFC 6455 5.4 lets a peer inject them between the fragments of a message. This is the
+ * stream hook's route for a frame whose glue leaves pktype == 0 (net_channel_ex.c:125-126,
+ * 155: straight to on_recv, past the fragment cache, never checked against
+ * readcache_max_size nor counted in cache_recv_bytes); pair it with
+ * websocketframeOnDecodeControl (wsframe_amd_channel.h). Per segment:
+ *   - every control frame is one message of its own: first_frame = its frame index,
+ *     n_frames = 1, complete = 1, continued = 0, len = datalen (0 allowed); it leaves the
+ *     pending message, d_open and d_cached alone and is never refused by the cache limit,
+ *     whatever its FIN bit;
+ *   - all other (data) frames follow the rule above among themselves, as if the control
+ *     frames were not there; a data message's first_frame is its first data frame in this
+ *     batch and n_frames counts its data frames only;
+ *   - message descriptors come in delivery order (ascending index of the delivering frame:
+ *     the control frame itself, or the data frame with FIN); a message still open at the
+ *     segment end comes last, and only if it has a data frame in this batch. A message's
+ *     opcode is d_desc[first_frame].type;
+ *   - bodies: data frame k's at region + (sum of datalen of the data frames before k), so a
+ *     data message stays contiguous; control frame k's at region + seg_len[s] - (sum of
+ *     datalen of the control frames up to and including k): control bodies are packed
+ *     downward from the region's end. A body larger than what is left of the region between
+ *     the two groups stops the bodies with WEBSOCKET_SEG_ERR_OUT_SPACE (datalen > seg_len -
+ *     the sum of all bodies before it), so the groups never meet; bytes between them are
+ *     never written.
+ * Descriptors and d_res equal the flag-off call's except where the cache limit stops a
+ * segment (control bodies are not counted, so that position can differ).
+ * Exported by libwsframe_amd_ctl.so (WSFRAME_AMD_CTL_EXPORT above), not by libwsframe_amd.so. */
+#define WEBSOCKET_REASM_CONTROL_DIRECT 1u
+WSFRAME_AMD_CTL_EXPORT int websocketframeBatchReassembleDeviceCtl(const unsigned char* d_buf, unsigned long long buflen,
+                                                              const unsigned long long* d_seg_off,
+                                                              const unsigned long long* d_seg_len, unsigned int nseg,
+                                                              unsigned int max_frames, WebsocketFrameDesc_t* d_desc,
+                                                              WebsocketSegResult_t* d_res, unsigned char* d_out,
+                                                              const unsigned long long* d_out_off,
+                                                              WebsocketMsgDesc_t* d_msg, unsigned int* d_nmsg,
+                                                              unsigned char* d_open, unsigned int readcache_max_size,
+                                                              unsigned int* d_cached, unsigned int flags,
+                                                              void* hip_stream);
 
 /* ---- Part 2c: batch encode + client masking -------------- */
 

@@ -84,6 +84,20 @@ typedef struct WebsocketBatchCursor_t {
 WSFRAME_AMD_EXPORT void websocketframeOnDecodeBatch(WebsocketBatchCursor_t* cursor, unsigned char* buf, size_t len,
                                                     struct NetChannelInbufDecodeResult_t* result);
 
+/* The RFC 6455 5.4 glue: as websocketframeOnDecode / websocketframeOnDecodeBatch, but a
+ * control frame (PING, PONG, CLOSE: type & 8; the batch variant reads the descriptor's type)
+ * keeps pktype = 0, so the stream hook hands it straight to on_recv (net_channel_ex.c:125-126,
+ * 155) instead of caching it as a fragment of the pending message: a ping between the
+ * fragments of a message neither joins nor closes it, and is never held against
+ * readcache_max_size. Registered as NetChannelExProc_t.on_decode exactly like
+ * websocketframeOnDecode; the GPU counterpart is websocketframeBatchReassembleDeviceCtl with
+ * WEBSOCKET_REASM_CONTROL_DIRECT. Both are exported by libwsframe_amd_ctl.so
+ * (WSFRAME_AMD_CTL_EXPORT, wsframe_amd.h), not by libwsframe_amd.so. */
+WSFRAME_AMD_CTL_EXPORT void websocketframeOnDecodeControl(struct NetChannel_t* channel, unsigned char* buf, size_t len,
+                                                      struct NetChannelInbufDecodeResult_t* result);
+WSFRAME_AMD_CTL_EXPORT void websocketframeOnDecodeBatchControl(WebsocketBatchCursor_t* cursor, unsigned char* buf,
+                                                           size_t len, struct NetChannelInbufDecodeResult_t* result);
+
 #ifdef __cplusplus
 }
 #endif

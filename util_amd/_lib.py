@@ -42,6 +42,12 @@ EXPORTS = REFERENCE_EXPORTS + [
     "websocketframeGpuLastError", "websocketframeGpuSetOption", "websocketframeGpuGetStat",
     "websocketframeOnDecode", "websocketframeOnDecodeBatch",
 ]
+# libwsframe_amd_ctl.so: the same objects, with the WSFRAME_AMD_CTL_EXPORT entry points exported too
+CTL_LIB_PATH = os.path.join(HERE, "libwsframe_amd_ctl.so")
+CTL_EXPORTS = ["websocketframeBatchReassembleDeviceCtl", "websocketframeOnDecodeControl",
+               "websocketframeOnDecodeBatchControl"]
+_ctl = None
+_options = {}            # options set through set_option(): libwsframe_amd_ctl.so keeps its own copy
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -120,12 +126,57 @@ def load_lib():
     lib.websocketframeOnDecode.argtypes = [vp, vp, C.c_size_t, vp]
     lib.websocketframeOnDecodeBatch.restype = None
     lib.websocketframeOnDecodeBatch.argtypes = [vp, vp, C.c_size_t, vp]
-    # launch tuning from the environment, e.g. WSFRAME_AMD_OPTIONS="path=0,seg_cfg=10"
+    _env_options(lib)
+    _lib = lib
+    return lib
+
+
+def _env_options(lib):
+    """launch tuning from the environment, e.g. WSFRAME_AMD_OPTIONS=path=0,seg_cfg=10"""
     for kv in filter(None, os.environ.get("WSFRAME_AMD_OPTIONS", "").split(",")):
         name, _, value = kv.partition("=")
         if lib.websocketframeGpuSetOption(name.strip().encode(), int(value)) != 0:
             raise ValueError("WSFRAME_AMD_OPTIONS: unknown option %r" % name)
-    _lib = lib
+
+
+def set_option(name, value):
+    """websocketframeGpuSetOption on libwsframe_amd.so and, once loaded, on libwsframe_amd_ctl.so
+    (options are per library: the two do not share state). Returns the C return code."""
+    rc = load_lib().websocketframeGpuSetOption(name.encode(), int(value))
+    if rc == 0:
+        _options[name] = int(value)
+        if _ctl is not None:
+            _ctl.websocketframeGpuSetOption(name.encode(), int(value))
+    return rc
+
+
+def load_ctl_lib():
+    """libwsframe_amd_ctl.so: websocketframeBatchReassembleDeviceCtl and the control-direct glue.
+    A library of its own state (workspace, options, last error): the options set so far through
+    set_option() are applied when it loads and forwarded afterwards."""
+    global _ctl
+    if _ctl is not None:
+        return _ctl
+    load_lib()
+    if not os.path.exists(CTL_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_ctl.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(CTL_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchReassembleDeviceCtl.restype = i32
+    lib.websocketframeBatchReassembleDeviceCtl.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp,
+                                                           u32, vp]
+    lib.websocketframeOnDecodeControl.restype = None
+    lib.websocketframeOnDecodeControl.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.websocketframeOnDecodeBatchControl.restype = None
+    lib.websocketframeOnDecodeBatchControl.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _ctl = lib
     return lib
 
 
@@ -157,9 +208,9 @@ def load_bench_lib():
     return lib
 
 
-def check(rc, what):
+def check(rc, what, lib=None):
     if rc != 0:
-        err = load_lib().websocketframeGpuLastError().decode(errors="replace")
+        err = (lib or load_lib()).websocketframeGpuLastError().decode(errors="replace")
         raise RuntimeError("%s failed (%d): %s" % (what, rc, err))
 
 

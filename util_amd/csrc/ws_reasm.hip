@@ -26,6 +26,16 @@
 // stop the segment there with WEBSOCKET_SEG_ERR_CACHE_OVERFLOW (descriptor written, not
 // consumed, no body). Cached bytes are counted in u32 as the reference's
 // StreamTransportCtx_t.cache_recv_bytes (transport_ctx.c:179-201) and carried across batches.
+//
+// Control frames delivered apart (websocketframeBatchReassembleDeviceCtl,
+// WEBSOCKET_REASM_CONTROL_DIRECT; template parameter CTL of both kernels): a consumed frame
+// with type & 8 takes the hook's pktype == 0 route (net_channel_ex.c:125-126, 155) — one
+// message of its own, past the pending message and the fragment cache. Data frames follow the
+// rule above among themselves. Data bodies go upward from the region's start (running sum of
+// the data bodies), control bodies downward from its end (running sum of the control bodies);
+// a body that does not fit between the two stops the bodies (WEBSOCKET_SEG_ERR_OUT_SPACE).
+// Message descriptors come in the order of the delivering frames. The flag-off instantiations
+// keep the earlier round verbatim (same registers, spills and occupancy).
 #include "ws_common.h"
 
 // check_cache_overflow (net_channel_ex.c:45-53) on u32 counts
@@ -50,6 +60,7 @@ struct GatherRec {       // 32 B per body, slot s*max_frames + body index
 // R2 with LG lanes per segment: lane j takes frame k0 + j of each round of LG frames;
 // body offsets are a group prefix sum, message boundaries come from the group's FIN mask.
 #define RLAY_G 16
+template <bool CTL>      // WEBSOCKET_REASM_CONTROL_DIRECT (see the file header)
 __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
     const unsigned char* __restrict__ buf, u32 nseg, u32 max_frames, const u64* __restrict__ seg_off,
     const u64* __restrict__ seg_len, const WebsocketFrameDesc_t* __restrict__ desc, WebsocketSegResult_t* __restrict__ res,
@@ -71,6 +82,8 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
     u32 cached = open && cached_io ? cached_io[sc] : 0u;                     // bytes of the pending message
     u32 nm = 0, nb = 0, first = 0;                                           // group-uniform state
     u64 q = 0, q0 = 0;
+    u64 qc = 0;                                                              // CTL: control body bytes so far (q: data bytes)
+    u32 mcnt = 0;                                                            // CTL: data frames of the pending message
     bool stop = false, overflow = false;
     int cstop_frame = -1;                                                    // frame refused by the cache limit
     const u64 gmask = (1ull << G) - 1;
@@ -87,6 +100,8 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
         const u32 nbody_r = badm ? (u32)__builtin_ctzll(badm) : (u32)__builtin_popcountll(inm);
         const bool body = gl < nbody_r;
         const u64 len = body ? d.datalen : 0;
+        const bool ctl = CTL && body && (d.type & 8);                        // control frame: a message by itself
+        const bool dat = body && !ctl;
         // inclusive prefix sum of the body lengths within the group
         u64 incl = len;
 #pragma unroll
@@ -94,27 +109,46 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
             const u64 t = __shfl_up(incl, o, G);
             if (gl >= o) incl += t;
         }
-        const u64 qs = q + incl - len;                                       // this body's output offset
+        u64 kincl = 0;                                                       // the control bodies' share of incl
+        if constexpr (CTL) {
+            kincl = ctl ? len : 0;
+#pragma unroll
+            for (u32 o = 1; o < G; o <<= 1) {
+                const u64 t = __shfl_up(kincl, o, G);
+                if (gl >= o) kincl += t;
+            }
+        }
+        const u64 dincl = incl - kincl;                                      // the data bodies' share
+        const u64 qs = q + dincl - (ctl ? 0 : len);                          // data bytes before this body
+        const u64 qa = qs + qc + kincl - (ctl ? len : 0);                    // all body bytes before it
         // bodies must fit the segment's region (only the (int) return quirk can break this)
-        const u64 ovm = (__ballot(body && len > sl - qs) >> gb) & gmask;   // qs <= sl before the first overflow
+        const u64 ovm = (__ballot(body && len > sl - qa) >> gb) & gmask;   // qa <= sl before the first overflow
         u32 ntake = ovm ? (u32)__builtin_ctzll(ovm) : nbody_r;
         // the fragment cache's limit: pending before frame k = frame k-1 was not FIN (lane 0: the
-        // carried state); cached bytes before k = the current message's bodies before k (u32)
-        const u32 blen = (u32)len;
+        // carried state); cached bytes before k = the current message's bodies before k (u32);
+        // CTL: both over the data frames only
+        const u32 blen = ctl ? 0u : (u32)len;
         u32 cincl = blen;
 #pragma unroll
         for (u32 o = 1; o < G; o <<= 1) {
             const u32 t = (u32)__shfl_up((int)cincl, o, G);
             if (gl >= o) cincl += t;
         }
-        const bool finb = body && d.is_fin;
+        const bool finb = dat && d.is_fin;
         const u64 fin_all = (__ballot(finb) >> gb) & gmask;
         const u64 fin_below = fin_all & ((1ull << gl) - 1);
         const u32 lastf = fin_below ? 63 - __builtin_clzll(fin_below) : 0;
         const u32 cincl_lastf = (u32)__shfl((int)cincl, (int)(gb + lastf), 64);
         const u32 cbefore = fin_below ? cincl - blen - cincl_lastf : cached + cincl - blen;
-        const bool pend = gl == 0 ? open != 0 : !((fin_all >> (gl - 1)) & 1ull);
-        const u64 ccm = (__ballot(body && (pend || !d.is_fin) && ws_cache_overflow(cbefore, blen, cache_max)) >> gb) & gmask;
+        const u64 dat_all = (__ballot(dat) >> gb) & gmask;
+        bool pend;
+        if constexpr (CTL) {                                                 // the previous data lane was not FIN
+            const u64 db = dat_all & ((1ull << gl) - 1);
+            pend = db ? !((fin_all >> (63 - __builtin_clzll(db))) & 1ull) : open != 0;
+        } else {
+            pend = gl == 0 ? open != 0 : !((fin_all >> (gl - 1)) & 1ull);
+        }
+        const u64 ccm = (__ballot(dat && (pend || !d.is_fin) && ws_cache_overflow(cbefore, blen, cache_max)) >> gb) & gmask;
         const u32 cst = ccm ? (u32)__builtin_ctzll(ccm) : 64u;
         if (cst < ntake) {
             ntake = cst;
@@ -126,39 +160,83 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
             ws_item_unpack(it, p0, p1, rk);
             const u32 sh = 8u * (u32)(p0 & 3);
             const u32 key = sh ? (rk >> sh) | (rk << (32 - sh)) : rk;       // the frame's key (wire order)
-            const u64 dst = ob + qs + lead_o;
+            // data bodies upward from the region's start, control bodies downward from its end
+            const u64 dst = ob + (ctl ? sl - (qc + kincl) : qs) + lead_o;
             GatherRec r;
             r.src = p0; r.dst = dst; r.len = len; r.key = d.masked ? rotl32(key, 8u * (u32)(dst & 3)) : 0u; r.pad = 0;
             recs[base + nb + gl] = r;
         }
         // messages closed by FIN frames among the taken ones
-        const u64 finm = (__ballot(gl < ntake && d.is_fin) >> gb) & gmask;
+        const bool fin = gl < ntake && dat && d.is_fin;
+        const u64 finm = (__ballot(fin) >> gb) & gmask;
         const u64 below = finm & ((1ull << gl) - 1);                         // earlier FINs in this round
         const u32 prevl = below ? 63 - __builtin_clzll(below) : gl;
-        const u64 incl_prev = __shfl(incl, (int)(gb + prevl), 64);          // all lanes active here
-        if (gl < ntake && d.is_fin) {
-            const u32 mfirst = below ? k0 + prevl + 1 : first;
-            const u64 prevq = below ? q + incl_prev : q0;
-            WebsocketMsgDesc_t m;
-            m.out_off = ob + prevq; m.len = qs + len - prevq; m.first_frame = mfirst; m.n_frames = k + 1 - mfirst;
-            m.complete = 1; m.continued = below ? 0u : cont;
-            msg[base + nm + (u32)__builtin_popcountll(below)] = m;
+        const u64 incl_prev = __shfl(dincl, (int)(gb + prevl), 64);         // all lanes active here
+        if constexpr (!CTL) {
+            if (fin) {
+                const u32 mfirst = below ? k0 + prevl + 1 : first;
+                const u64 prevq = below ? q + incl_prev : q0;
+                WebsocketMsgDesc_t m;
+                m.out_off = ob + prevq; m.len = qs + len - prevq; m.first_frame = mfirst; m.n_frames = k + 1 - mfirst;
+                m.complete = 1; m.continued = below ? 0u : cont;
+                msg[base + nm + (u32)__builtin_popcountll(below)] = m;
+            }
         }
-        const u64 tot_l = __shfl(incl, (int)(gb + (ntake ? ntake - 1 : 0)), 64);
+        const u64 tot_l = __shfl(dincl, (int)(gb + (ntake ? ntake - 1 : 0)), 64);
         const u32 last = finm ? 63 - __builtin_clzll(finm) : 0;             // last FIN of the round
-        const u64 incl_last = __shfl(incl, (int)(gb + last), 64);
+        const u64 incl_last = __shfl(dincl, (int)(gb + last), 64);
         const u64 tot = ntake ? tot_l : 0;
         const u32 ctot = (u32)__shfl((int)cincl, (int)(gb + (ntake ? ntake - 1 : 0)), 64);
         const u32 clast = (u32)__shfl((int)cincl, (int)(gb + last), 64);
-        if (ntake) cached = finm ? (ntake > last + 1 ? ctot - clast : 0u) : cached + ctot;
-        if (finm) {
-            q0 = q + incl_last;
-            first = k0 + last + 1;
-            cont = 0;
-            open = ntake > last + 1 ? 1u : 0u;
-            nm += (u32)__builtin_popcountll(finm);
-        } else if (ntake) {
-            open = 1;
+        if constexpr (CTL) {
+            // a lane delivers if it is a control lane or a data lane with FIN; a data message's
+            // frames are the data lanes since the previous data FIN
+            const u64 tkm = (1ull << ntake) - 1;                             // ntake <= G < 64
+            const u64 dm = dat_all & tkm, cm = (__ballot(ctl) >> gb) & tkm;
+            const u64 lt = (1ull << gl) - 1;
+            const u32 slot = nm + (u32)__builtin_popcountll((finm | cm) & lt);
+            if (fin) {
+                const u64 mine = dm & (lt | (1ull << gl)) & ~(below ? (2ull << prevl) - 1 : 0ull);
+                const u64 prevq = below ? q + incl_prev : q0;
+                WebsocketMsgDesc_t m;
+                m.out_off = ob + prevq; m.len = qs + len - prevq;
+                m.first_frame = below || !mcnt ? k0 + (u32)__builtin_ctzll(mine) : first;
+                m.n_frames = (u32)__builtin_popcountll(mine) + (below ? 0u : mcnt);
+                m.complete = 1; m.continued = below ? 0u : cont;
+                msg[base + slot] = m;
+            } else if (gl < ntake && ctl) {
+                WebsocketMsgDesc_t m;
+                m.out_off = ob + (sl - (qc + kincl)); m.len = len; m.first_frame = k; m.n_frames = 1;
+                m.complete = 1; m.continued = 0;
+                msg[base + slot] = m;
+            }
+            const u64 rest = finm ? dm & ~((2ull << last) - 1) : dm;         // data lanes left pending
+            if (ntake) cached = finm ? ctot - clast : cached + ctot;
+            if (finm) {
+                q0 = q + incl_last;
+                cont = 0;
+                mcnt = 0;
+                open = 0;
+            }
+            if (rest) {
+                if (!mcnt) first = k0 + (u32)__builtin_ctzll(rest);
+                mcnt += (u32)__builtin_popcountll(rest);
+                open = 1;
+            }
+            nm += (u32)__builtin_popcountll(finm | cm);
+            const u64 ktot = __shfl(kincl, (int)(gb + (ntake ? ntake - 1 : 0)), 64);
+            qc += ntake ? ktot : 0;
+        } else {
+            if (ntake) cached = finm ? (ntake > last + 1 ? ctot - clast : 0u) : cached + ctot;
+            if (finm) {
+                q0 = q + incl_last;
+                first = k0 + last + 1;
+                cont = 0;
+                open = ntake > last + 1 ? 1u : 0u;
+                nm += (u32)__builtin_popcountll(finm);
+            } else if (ntake) {
+                open = 1;
+            }
         }
         q += tot;
         nb += ntake;
@@ -167,13 +245,13 @@ __global__ __launch_bounds__(RLAY_T) void ws_reasm_layout_kernel(
         if (!active) stop = true;
     }
     if (!active || gl != 0) return;
-    if (open && nb > first) {                                                // still open at the segment end
+    if (open && (CTL ? mcnt != 0 : nb > first)) {                            // still open at the segment end
         WebsocketMsgDesc_t m;
-        m.out_off = ob + q0; m.len = q - q0; m.first_frame = first; m.n_frames = nb - first;
+        m.out_off = ob + q0; m.len = q - q0; m.first_frame = first; m.n_frames = CTL ? mcnt : nb - first;
         m.complete = 0; m.continued = cont;
         msg[base + nm++] = m;
     }
-    if (cstop_frame >= 0) {                                                  // not consumed; the channel detaches
+    if (cstop_frame >= 0) {                                                 // not consumed; the channel detaches
         const WebsocketFrameDesc_t dc = desc[base + (u32)cstop_frame];
         ws_store_res(res + s, dc.frame_off - so, (u32)cstop_frame + 1, WEBSOCKET_SEG_ERR_CACHE_OVERFLOW);
     } else if (overflow) {
@@ -301,7 +379,8 @@ __device__ __forceinline__ void reasm_copy(const u32x4* win, u32 o0, u32 nch, u3
     }
 }
 
-template <int RSEG_L, int MINW>
+// CTL: WEBSOCKET_REASM_CONTROL_DIRECT (see the file header); false is the plain rule.
+template <int RSEG_L, int MINW, bool CTL = false>
 __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8))) void ws_reasm_seg_kernel(
     const unsigned char* __restrict__ buf, u32 max_frames, const u64* __restrict__ seg_off,
     const u64* __restrict__ seg_len, WebsocketFrameDesc_t* __restrict__ desc, WebsocketSegResult_t* __restrict__ res,
@@ -330,6 +409,8 @@ __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8)
     // wave-0 walk state (wave-uniform)
     u64 off = 0, g = 0, q = 0, q0 = 0;
     u32 nf = 0, nb = 0, nm = 0, first = 0;
+    u64 qc = 0;                                                      // CTL: control body bytes so far (q: data bytes)
+    u32 mcnt = 0;                                                    // CTL: data frames of the pending message in this batch
     int status = WEBSOCKET_SEG_OK;
     bool walking = true, bodies_on = true, overflow = false;
     u32 open = w0 && open_io ? open_io[s] : 0u, cont = open;
@@ -359,76 +440,178 @@ __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8)
                 // running sum of the bodies before it; none after an overflow
                 const u32 nbr = bodies_on ? mm + (code_m == 1 ? 1u : 0u) : 0u;
                 if (nbr) {
-                    const bool body = lane < nbr;
-                    const u64 len = body ? h.plen : 0;
-                    u64 incl = len;
+                    u32 cst;
+                    bool cref;
+                    if constexpr (!CTL) {                        // the plain rule
+                        const bool body = lane < nbr;
+                        const u64 len = body ? h.plen : 0;
+                        u64 incl = len;
 #pragma unroll
-                    for (u32 d = 1; d < 64; d <<= 1) {
-                        const u64 t = __shfl_up(incl, d, 64);
-                        if (lane >= d) incl += t;
-                    }
-                    const u64 qs = q + incl - len;
-                    // bodies must fit the segment's region (qs <= sl for every lane before the first overflow)
-                    const u64 ovm = __ballot(body && len > sl - qs);
-                    u32 ntb = ovm ? (u32)__builtin_ctzll(ovm) : nbr;
-                    // the fragment cache's limit (see the file header): pending before lane i =
-                    // frame i-1 not FIN (lane 0: carried), cached bytes = the message's bodies so far
-                    const u32 blen = (u32)len;
-                    u32 cincl = blen;
+                        for (u32 d = 1; d < 64; d <<= 1) {
+                            const u64 t = __shfl_up(incl, d, 64);
+                            if (lane >= d) incl += t;
+                        }
+                        const u64 qs = q + incl - len;
+                        // bodies must fit the segment's region (qs <= sl for every lane before the first overflow)
+                        const u64 ovm = __ballot(body && len > sl - qs);
+                        u32 ntb = ovm ? (u32)__builtin_ctzll(ovm) : nbr;
+                        // the fragment cache's limit (see the file header): pending before lane i =
+                        // frame i-1 not FIN (lane 0: carried), cached bytes = the message's bodies so far
+                        const u32 blen = (u32)len;
+                        u32 cincl = blen;
 #pragma unroll
-                    for (u32 d = 1; d < 64; d <<= 1) {
-                        const u32 t = (u32)__shfl_up((int)cincl, d, 64);
-                        if (lane >= d) cincl += t;
+                        for (u32 d = 1; d < 64; d <<= 1) {
+                            const u32 t = (u32)__shfl_up((int)cincl, d, 64);
+                            if (lane >= d) cincl += t;
+                        }
+                        const bool finl = h.b0 >> 7;
+                        const u64 fin_all = __ballot(body && finl);
+                        const u64 fin_below = fin_all & ((1ull << lane) - 1);
+                        const u32 lastf = fin_below ? 63 - __builtin_clzll(fin_below) : 0;
+                        const u32 cincl_lastf = (u32)__shfl((int)cincl, (int)lastf, 64);
+                        const u32 cbefore = fin_below ? cincl - blen - cincl_lastf : cached + cincl - blen;
+                        const bool pend = lane == 0 ? open != 0 : !((fin_all >> (lane - 1)) & 1ull);
+                        const u64 ccm = __ballot(body && (pend || !finl) && ws_cache_overflow(cbefore, blen, cache_max));
+                        cst = ccm ? (u32)__builtin_ctzll(ccm) : 64u;
+                        cref = cst < ntb;                       // refused before any out-of-space body
+                        if (cref) ntb = cst;
+                        else if (ovm) { bodies_on = false; overflow = true; }
+                        if (lane < ntb) {
+                            BodyL b;
+                            b.x0 = X + h.hdr; b.dst = qs; b.len = len;
+                            tab[nb + lane] = b;
+                            tkey[nb + lane] = h.masked ? rotl32(h.key, 8u * (u32)((obase + qs) & 3)) : 0u;
+                        }
+                        // messages closed by FIN frames among the taken bodies (body index == frame index)
+                        const bool fin = lane < ntb && (h.b0 >> 7);
+                        const u64 finm = __ballot(fin);
+                        const u64 below = finm & ((1ull << lane) - 1);
+                        const u32 prevl = below ? 63 - __builtin_clzll(below) : lane;
+                        const u64 incl_prev = __shfl(incl, (int)prevl, 64);
+                        if (fin) {
+                            WebsocketMsgDesc_t m;
+                            const u32 mfirst = below ? nb + prevl + 1 : first;
+                            const u64 prevq = below ? q + incl_prev : q0;
+                            m.out_off = ob + prevq; m.len = qs + len - prevq; m.first_frame = mfirst;
+                            m.n_frames = nb + lane + 1 - mfirst; m.complete = 1; m.continued = below ? 0u : cont;
+                            msg[base + nm + (u32)__builtin_popcountll(below)] = m;
+                        }
+                        const u64 tot = __shfl(incl, (int)(ntb ? ntb - 1 : 0), 64);
+                        const u32 last = finm ? 63 - __builtin_clzll(finm) : 0;
+                        const u64 incl_last = __shfl(incl, (int)last, 64);
+                        if (finm) {
+                            q0 = q + incl_last;
+                            first = nb + last + 1;
+                            cont = 0;
+                            open = ntb > last + 1 ? 1u : 0u;
+                            nm += (u32)__builtin_popcountll(finm);
+                        } else if (ntb) {
+                            open = 1;
+                        }
+                        const u32 ctot = (u32)__shfl((int)cincl, (int)(ntb ? ntb - 1 : 0), 64);
+                        const u32 clast = (u32)__shfl((int)cincl, (int)last, 64);
+                        if (ntb) cached = finm ? (ntb > last + 1 ? ctot - clast : 0u) : cached + ctot;
+                        q += ntb ? tot : 0;
+                        nb += ntb;
+                    } else {                                     // control frames delivered apart
+                        const bool body = lane < nbr;
+                        const u64 len = body ? h.plen : 0;
+                        const bool ctl = body && (h.b0 & 8);        // control frame: a message by itself
+                        const bool dat = body && !ctl;
+                        u64 incl = len;
+#pragma unroll
+                        for (u32 d = 1; d < 64; d <<= 1) {
+                            const u64 t = __shfl_up(incl, d, 64);
+                            if (lane >= d) incl += t;
+                        }
+                        u64 kincl = ctl ? len : 0;                   // the control bodies' share of incl
+#pragma unroll
+                        for (u32 d = 1; d < 64; d <<= 1) {
+                            const u64 t = __shfl_up(kincl, d, 64);
+                            if (lane >= d) kincl += t;
+                        }
+                        const u64 dincl = incl - kincl;              // the data bodies' share
+                        const u64 qs = q + dincl - (ctl ? 0 : len); // data bytes before this body
+                        const u64 qa = qs + qc + kincl - (ctl ? len : 0);   // all body bytes before it
+                        // bodies must fit the segment's region (qa <= sl for every lane before the first overflow)
+                        const u64 ovm = __ballot(body && len > sl - qa);
+                        u32 ntb = ovm ? (u32)__builtin_ctzll(ovm) : nbr;
+                        // the fragment cache's limit (see the file header): pending before lane i =
+                        // frame i-1 not FIN (lane 0: carried), cached bytes = the message's bodies so far
+                        // over the data frames only (the u32 prefix sum of their lengths is dincl's low half)
+                        const u32 blen = ctl ? 0u : (u32)len;
+                        const u32 cincl = (u32)dincl;
+                        const bool finl = h.b0 >> 7;
+                        const u64 fin_all = __ballot(dat && finl);
+                        const u64 fin_below = fin_all & ((1ull << lane) - 1);
+                        const u32 lastf = fin_below ? 63 - __builtin_clzll(fin_below) : 0;
+                        const u32 cincl_lastf = (u32)__shfl((int)cincl, (int)lastf, 64);
+                        const u32 cbefore = fin_below ? cincl - blen - cincl_lastf : cached + cincl - blen;
+                        const u64 db = __ballot(dat) & ((1ull << lane) - 1);   // pending: the previous data lane was not FIN
+                        const bool pend = db ? !((fin_all >> (63 - __builtin_clzll(db))) & 1ull) : open != 0;
+                        const u64 ccm = __ballot(dat && (pend || !finl) && ws_cache_overflow(cbefore, blen, cache_max));
+                        cst = ccm ? (u32)__builtin_ctzll(ccm) : 64u;
+                        cref = cst < ntb;                       // refused before any out-of-space body
+                        if (cref) ntb = cst;
+                        else if (ovm) { bodies_on = false; overflow = true; }
+                        if (lane < ntb) {
+                            BodyL b;
+                            // data bodies upward from the region's start, control bodies downward from its end
+                            b.x0 = X + h.hdr; b.dst = ctl ? sl - (qc + kincl) : qs; b.len = len;
+                            tab[nb + lane] = b;
+                            tkey[nb + lane] = h.masked ? rotl32(h.key, 8u * (u32)((obase + b.dst) & 3)) : 0u;
+                        }
+                        // messages closed by FIN frames among the taken bodies (body index == frame index)
+                        const bool fin = lane < ntb && dat && (h.b0 >> 7);
+                        const u64 finm = __ballot(fin);
+                        const u64 below = finm & ((1ull << lane) - 1);
+                        const u32 prevl = below ? 63 - __builtin_clzll(below) : lane;
+                        const u64 incl_prev = __shfl(dincl, (int)prevl, 64);
+                        const u64 tot = __shfl(dincl, (int)(ntb ? ntb - 1 : 0), 64);
+                        const u32 last = finm ? 63 - __builtin_clzll(finm) : 0;
+                        const u64 incl_last = __shfl(dincl, (int)last, 64);
+                        // a lane delivers if it is a control lane or a data lane with FIN; a data
+                        // message's frames are the data lanes since the previous data FIN
+                        const u64 tkm = ntb < 64 ? (1ull << ntb) - 1 : ~0ull;
+                        const u64 dm = __ballot(dat) & tkm, cm = __ballot(ctl) & tkm;
+                        const u64 lt = (1ull << lane) - 1;
+                        const u32 slot = nm + (u32)__builtin_popcountll((finm | cm) & lt);
+                        if (fin) {
+                            WebsocketMsgDesc_t m;
+                            const u64 mine = dm & (lt | (1ull << lane)) & ~(below ? (2ull << prevl) - 1 : 0ull);
+                            const u64 prevq = below ? q + incl_prev : q0;
+                            m.out_off = ob + prevq; m.len = qs + len - prevq;
+                            m.first_frame = below || !mcnt ? nb + (u32)__builtin_ctzll(mine) : first;
+                            m.n_frames = (u32)__builtin_popcountll(mine) + (below ? 0u : mcnt);
+                            m.complete = 1; m.continued = below ? 0u : cont;
+                            msg[base + slot] = m;
+                        } else if (lane < ntb && ctl) {
+                            WebsocketMsgDesc_t m;
+                            m.out_off = ob + (sl - (qc + kincl)); m.len = len; m.first_frame = nb + lane;
+                            m.n_frames = 1; m.complete = 1; m.continued = 0;
+                            msg[base + slot] = m;
+                        }
+                        const u64 rest = finm ? dm & ~((2ull << last) - 1) : dm;   // data lanes left pending
+                        if (finm) {
+                            q0 = q + incl_last;
+                            cont = 0;
+                            mcnt = 0;
+                            open = 0;
+                        }
+                        if (rest) {
+                            if (!mcnt) first = nb + (u32)__builtin_ctzll(rest);
+                            mcnt += (u32)__builtin_popcountll(rest);
+                            open = 1;
+                        }
+                        nm += (u32)__builtin_popcountll(finm | cm);
+                        const u32 ctot = (u32)__shfl((int)cincl, (int)(ntb ? ntb - 1 : 0), 64);
+                        const u32 clast = (u32)__shfl((int)cincl, (int)last, 64);
+                        if (ntb) cached = finm ? ctot - clast : cached + ctot;
+                        const u64 ktot = __shfl(kincl, (int)(ntb ? ntb - 1 : 0), 64);
+                        qc += ntb ? ktot : 0;
+                        q += ntb ? tot : 0;
+                        nb += ntb;
                     }
-                    const bool finl = h.b0 >> 7;
-                    const u64 fin_all = __ballot(body && finl);
-                    const u64 fin_below = fin_all & ((1ull << lane) - 1);
-                    const u32 lastf = fin_below ? 63 - __builtin_clzll(fin_below) : 0;
-                    const u32 cincl_lastf = (u32)__shfl((int)cincl, (int)lastf, 64);
-                    const u32 cbefore = fin_below ? cincl - blen - cincl_lastf : cached + cincl - blen;
-                    const bool pend = lane == 0 ? open != 0 : !((fin_all >> (lane - 1)) & 1ull);
-                    const u64 ccm = __ballot(body && (pend || !finl) && ws_cache_overflow(cbefore, blen, cache_max));
-                    const u32 cst = ccm ? (u32)__builtin_ctzll(ccm) : 64u;
-                    const bool cref = cst < ntb;                 // refused before any out-of-space body
-                    if (cref) ntb = cst;
-                    else if (ovm) { bodies_on = false; overflow = true; }
-                    if (lane < ntb) {
-                        BodyL b;
-                        b.x0 = X + h.hdr; b.dst = qs; b.len = len;
-                        tab[nb + lane] = b;
-                        tkey[nb + lane] = h.masked ? rotl32(h.key, 8u * (u32)((obase + qs) & 3)) : 0u;
-                    }
-                    // messages closed by FIN frames among the taken bodies (body index == frame index)
-                    const bool fin = lane < ntb && (h.b0 >> 7);
-                    const u64 finm = __ballot(fin);
-                    const u64 below = finm & ((1ull << lane) - 1);
-                    const u32 prevl = below ? 63 - __builtin_clzll(below) : lane;
-                    const u64 incl_prev = __shfl(incl, (int)prevl, 64);
-                    if (fin) {
-                        WebsocketMsgDesc_t m;
-                        const u32 mfirst = below ? nb + prevl + 1 : first;
-                        const u64 prevq = below ? q + incl_prev : q0;
-                        m.out_off = ob + prevq; m.len = qs + len - prevq; m.first_frame = mfirst;
-                        m.n_frames = nb + lane + 1 - mfirst; m.complete = 1; m.continued = below ? 0u : cont;
-                        msg[base + nm + (u32)__builtin_popcountll(below)] = m;
-                    }
-                    const u64 tot = __shfl(incl, (int)(ntb ? ntb - 1 : 0), 64);
-                    const u32 last = finm ? 63 - __builtin_clzll(finm) : 0;
-                    const u64 incl_last = __shfl(incl, (int)last, 64);
-                    if (finm) {
-                        q0 = q + incl_last;
-                        first = nb + last + 1;
-                        cont = 0;
-                        open = ntb > last + 1 ? 1u : 0u;
-                        nm += (u32)__builtin_popcountll(finm);
-                    } else if (ntb) {
-                        open = 1;
-                    }
-                    const u32 ctot = (u32)__shfl((int)cincl, (int)(ntb ? ntb - 1 : 0), 64);
-                    const u32 clast = (u32)__shfl((int)cincl, (int)last, 64);
-                    if (ntb) cached = finm ? (ntb > last + 1 ? ctot - clast : 0u) : cached + ctot;
-                    q += ntb ? tot : 0;
-                    nb += ntb;
                     if (cref) {                              // refused: not consumed, the walk ends there
                         off = __shfl(pos, (int)cst, 64);
                         nf += cst + 1;
@@ -460,7 +643,7 @@ __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8)
         // assembled whole by body j's wave when both bodies cover it from this window (one 16-B
         // store instead of byte stores from two waves): bit j of mg.
         u64 mg = 0;
-        if (merge) {
+        if (!CTL && merge) {                                             // (bodies adjacent in frame order only)
             const u64 px0 = __shfl_up(t.x0, 1, 64), pdst = __shfl_up(t.dst, 1, 64), plen = __shfl_up(t.len, 1, 64);
             const u64 da = obase + t.dst, C0 = da & ~15ull;
             const bool ok = lane > blo && lane <= bhi && (da & 15) && t.len && plen >= da - C0 &&
@@ -527,9 +710,9 @@ __global__ __launch_bounds__(RSEG_T) __attribute__((amdgpu_waves_per_eu(MINW, 8)
         wc = nxt;
     }
     if (tid != 0) return;
-    if (open && nb > first) {                                                // still open at the segment end
+    if (open && (CTL ? mcnt != 0 : nb > first)) {                            // still open at the segment end
         WebsocketMsgDesc_t m;
-        m.out_off = ob + q0; m.len = q - q0; m.first_frame = first; m.n_frames = nb - first;
+        m.out_off = ob + q0; m.len = q - q0; m.first_frame = first; m.n_frames = CTL ? mcnt : nb - first;
         m.complete = 0; m.continued = cont;
         msg[base + nm++] = m;
     }
@@ -547,11 +730,15 @@ WsOpt ws_reasm_path{0};
 // occupancy (7 waves/SIMD), 2 19 KiB windows
 WsOpt ws_reasm_cfg{0};
 
-extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(
+extern "C" WSFRAME_AMD_CTL_EXPORT int websocketframeBatchReassembleDeviceCtl(
     const unsigned char* d_buf, unsigned long long buflen, const u64* d_seg_off, const u64* d_seg_len,
     unsigned int nseg, unsigned int max_frames, WebsocketFrameDesc_t* d_desc, WebsocketSegResult_t* d_res,
     unsigned char* d_out, const u64* d_out_off, WebsocketMsgDesc_t* d_msg, unsigned int* d_nmsg,
-    unsigned char* d_open, unsigned int readcache_max_size, unsigned int* d_cached, void* hip_stream) {
+    unsigned char* d_open, unsigned int readcache_max_size, unsigned int* d_cached, unsigned int flags,
+    void* hip_stream) {
+    if (flags & ~WEBSOCKET_REASM_CONTROL_DIRECT)
+        return ws_set_msg("websocketframeBatchReassembleDeviceCtl: unknown flag bit");
+    const bool ctl = (flags & WEBSOCKET_REASM_CONTROL_DIRECT) != 0;
     if (nseg == 0) return 0;
     if (!d_buf || !d_seg_off || !d_seg_len || !d_desc || !d_res || !d_out || !d_msg || !d_nmsg || max_frames == 0)
         return ws_set_msg("websocketframeBatchReassembleDevice: invalid argument");
@@ -564,6 +751,9 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(
     const bool fused = rpath == 1 || (rpath == 0 && max_frames <= RSEG_TB && nseg >= 1024 && buflen <= (u64)nseg << 18);
     if (fused && max_frames <= RSEG_TB) {
         auto k = rcfg == 1 ? ws_reasm_seg_kernel<18, 1> : (rcfg == 2 ? ws_reasm_seg_kernel<20, 1> : ws_reasm_seg_kernel<18, 8>);
+        if (ctl)
+            k = rcfg == 1 ? ws_reasm_seg_kernel<18, 1, true>
+                          : (rcfg == 2 ? ws_reasm_seg_kernel<20, 1, true> : ws_reasm_seg_kernel<18, 8, true>);
         const int swin = ws_seg_win;                                   // one read per call
         const WsWinGrid wg = ws_win_grid(nseg, swin < 0 ? 3 : swin);
         // (body-boundary chunks: one byte-store instruction from 31 lanes; one lane assembling
@@ -591,7 +781,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(
     L.cus = slot.cus; L.lds_per_cu = slot.lds;
     PieceWs P;
     if ((rc = ws_launch_piece_scan(L, 0, buflen, w8, ws_next_gen(), &P))) return rc;
-    hipLaunchKernelGGL(ws_reasm_layout_kernel, dim3((u32)(((u64)nseg * RLAY_G + RLAY_T - 1) / RLAY_T)), dim3(RLAY_T), 0, st, d_buf, nseg,
+    hipLaunchKernelGGL(ctl ? ws_reasm_layout_kernel<true> : ws_reasm_layout_kernel<false>, dim3((u32)(((u64)nseg * RLAY_G + RLAY_T - 1) / RLAY_T)), dim3(RLAY_T), 0, st, d_buf, nseg,
                        max_frames, d_seg_off, d_seg_len, d_desc, d_res, P.items, d_out, d_out_off, d_msg, d_nmsg,
                        d_open, recs, nbody, (u32)readcache_max_size, d_cached);
     hipError_t e = hipGetLastError();
@@ -603,6 +793,16 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(
                        recs, nbody);
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_reasm_gather_kernel launch", e);
     return 0;
+}
+
+extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDeviceEx(
+    const unsigned char* d_buf, unsigned long long buflen, const u64* d_seg_off, const u64* d_seg_len,
+    unsigned int nseg, unsigned int max_frames, WebsocketFrameDesc_t* d_desc, WebsocketSegResult_t* d_res,
+    unsigned char* d_out, const u64* d_out_off, WebsocketMsgDesc_t* d_msg, unsigned int* d_nmsg,
+    unsigned char* d_open, unsigned int readcache_max_size, unsigned int* d_cached, void* hip_stream) {
+    return websocketframeBatchReassembleDeviceCtl(d_buf, buflen, d_seg_off, d_seg_len, nseg, max_frames, d_desc, d_res,
+                                                  d_out, d_out_off, d_msg, d_nmsg, d_open, readcache_max_size, d_cached,
+                                                  0u, hip_stream);
 }
 
 extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchReassembleDevice(

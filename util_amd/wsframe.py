@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import WsDesc, WsSegRes, check, check_bench, load_bench_lib, load_lib
+from . import _lib
+from ._lib import WsDesc, WsSegRes, check, check_bench, load_bench_lib, load_ctl_lib, load_lib
 
 WEBSOCKET_CONTINUE_FRAME = 0
 WEBSOCKET_TEXT_FRAME = 1
@@ -23,6 +24,7 @@ WEBSOCKET_MAX_ENCODE_HEADLENGTH = 10
 SEG_OK, SEG_MAX_FRAMES, SEG_ERR_DECODE, SEG_ERR_LEN_WRAP = 0, 1, -1, -2
 SEG_ERR_OUT_SPACE = -3
 SEG_ERR_CACHE_OVERFLOW = -4
+REASM_CONTROL_DIRECT = 1  # WEBSOCKET_REASM_CONTROL_DIRECT: control frames delivered apart from fragmented messages
 NETPACKET_FRAGMENT = 6  # transport_ctx.h:11-18; the pktype websocketframeOnDecode reports
 DATA_OFF_NULL = 0xFFFFFFFFFFFFFFFF
 BATCH_PAD = 32  # WEBSOCKET_BATCH_PAD: readable device bytes required after every segment
@@ -160,19 +162,28 @@ def stream_decode_device(buf, length, max_frames, desc, res, stream=None):
 
 
 def batch_reassemble_device(buf, seg_off, seg_len, max_frames, desc, res, out, msg, nmsg, out_off=None, open_state=None,
-                            stream=None, readcache_max=0, cached=None):
+                            stream=None, readcache_max=0, cached=None, flags=0):
     """websocketframeBatchReassembleDeviceEx on torch CUDA tensors: buf (uint8, wire, read only;
     the last BATCH_PAD bytes are slack), seg_off/seg_len/out_off (int64), desc (uint8
     >= 32*nseg*max_frames), res (uint8 16*nseg), out (uint8), msg (uint8 >= 32*nseg*max_frames),
     nmsg (int32 nseg), open_state (uint8 nseg, in/out, optional), readcache_max (the channel's
     readcache_max_size, 0 = unlimited), cached (int32 nseg, in/out, optional: the pending
-    message's cached bytes, u32); async on `stream`."""
+    message's cached bytes, u32); async on `stream`. flags: 0, or REASM_CONTROL_DIRECT
+    (websocketframeBatchReassembleDeviceCtl of libwsframe_amd_ctl.so: every control frame is a message of its own, its
+    body packed downward from its region's end)."""
     nseg = seg_off.numel()
     assert buf.numel() >= BATCH_PAD and seg_len.numel() == nseg and nmsg.numel() >= nseg
     assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
     assert msg.numel() * msg.element_size() >= 32 * nseg * max_frames
     assert res.numel() * res.element_size() >= 16 * nseg
     assert cached is None or cached.numel() * cached.element_size() >= 4 * nseg
+    if flags:
+        rc = load_ctl_lib().websocketframeBatchReassembleDeviceCtl(
+            _ptr(buf), buf.numel() - BATCH_PAD, _ptr(seg_off), _ptr(seg_len), nseg, max_frames, _ptr(desc), _ptr(res),
+            _ptr(out), _ptr(out_off), _ptr(msg), _ptr(nmsg), _ptr(open_state), int(readcache_max), _ptr(cached),
+            int(flags), _stream(stream))
+        check(rc, "websocketframeBatchReassembleDeviceCtl", load_ctl_lib())
+        return
     rc = load_lib().websocketframeBatchReassembleDeviceEx(
         _ptr(buf), buf.numel() - BATCH_PAD, _ptr(seg_off), _ptr(seg_len), nseg, max_frames, _ptr(desc), _ptr(res),
         _ptr(out), _ptr(out_off), _ptr(msg), _ptr(nmsg), _ptr(open_state), int(readcache_max), _ptr(cached),
@@ -250,7 +261,7 @@ def frame_hash_device(buf, desc, res, nseg, max_frames, out, stream=None):
 
 def set_option(name, value):
     """websocketframeGpuSetOption (launch tuning knobs, for A/B measurement)"""
-    rc = load_lib().websocketframeGpuSetOption(name.encode(), int(value))
+    rc = _lib.set_option(name, value)          # both libraries
     if rc != 0:
         raise ValueError("unknown option %r" % name)
 
