@@ -47,7 +47,12 @@ CTL_LIB_PATH = os.path.join(HERE, "libwsframe_amd_ctl.so")
 CTL_EXPORTS = ["websocketframeBatchReassembleDeviceCtl", "websocketframeOnDecodeControl",
                "websocketframeOnDecodeBatchControl"]
 _ctl = None
-_options = {}            # options set through set_option(): libwsframe_amd_ctl.so keeps its own copy
+# libwsframe_amd_text.so: everything libwsframe_amd_ctl.so exports plus the WSFRAME_AMD_TEXT_EXPORT
+# entry point (include/wsframe_amd_text.h)
+TEXT_LIB_PATH = os.path.join(HERE, "libwsframe_amd_text.so")
+TEXT_EXPORTS = ["websocketframeBatchValidateTextDevice"]
+_text = None
+_options = {}            # options set through set_option(): the ctl and text libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -147,6 +152,8 @@ def set_option(name, value):
         _options[name] = int(value)
         if _ctl is not None:
             _ctl.websocketframeGpuSetOption(name.encode(), int(value))
+        if _text is not None:
+            _text.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -177,6 +184,41 @@ def load_ctl_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _ctl = lib
+    return lib
+
+
+def load_text_lib():
+    """libwsframe_amd_text.so: websocketframeBatchValidateTextDevice next to the whole C ABI of
+    libwsframe_amd_ctl.so (one library for a text server). A library of its own state, as
+    load_ctl_lib(): the options set so far are applied when it loads and forwarded afterwards."""
+    global _text
+    if _text is not None:
+        return _text
+    load_lib()
+    if not os.path.exists(TEXT_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_text.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(TEXT_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchValidateTextDevice.restype = i32
+    lib.websocketframeBatchValidateTextDevice.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.websocketframeBatchReassembleDevice.restype = i32
+    lib.websocketframeBatchReassembleDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.websocketframeBatchReassembleDeviceEx.restype = i32
+    lib.websocketframeBatchReassembleDeviceEx.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp,
+                                                          vp]
+    lib.websocketframeBatchReassembleDeviceCtl.restype = i32
+    lib.websocketframeBatchReassembleDeviceCtl.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp,
+                                                           u32, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    lib.websocketframeGpuGetStat.restype = i32
+    lib.websocketframeGpuGetStat.argtypes = [C.c_char_p, C.POINTER(C.c_ulonglong)]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _text = lib
     return lib
 
 

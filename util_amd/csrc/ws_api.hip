@@ -198,6 +198,8 @@ struct WsStreamWs {
     size_t ws_bytes = 0;
     void* ews = nullptr;           // encode workspace (scan temp + piece pointers)
     size_t ews_bytes = 0;
+    void* tws = nullptr;           // text validation workspace (ws_utf8.hip: per-slot records + tile scan)
+    size_t tws_bytes = 0;
     void* aws = nullptr;           // auxiliary device scratch (the stream path's chunk-parallel walk)
     size_t aws_bytes = 0;
     void* hws = nullptr;           // ... and its pinned host copy
@@ -228,7 +230,7 @@ size_t ws_workspace_bytes_total() {
     size_t t = 0;
     for (auto& d : g_dev) {
         for (auto& w : d.sw) {
-            t += w.ws_bytes + w.ews_bytes + w.aws_bytes;
+            t += w.ws_bytes + w.ews_bytes + w.aws_bytes + w.tws_bytes;
             for (auto& r : w.retired) t += r.second;
         }
         for (auto& r : d.deferred) t += r.second;
@@ -272,14 +274,15 @@ static bool capturing(hipStream_t stream) {
 static void slot_free(WsStreamWs& w) {
     (void)hipFree(w.ws);
     (void)hipFree(w.ews);
+    (void)hipFree(w.tws);
     (void)hipFree(w.aws);
     if (w.hws) (void)hipHostFree(w.hws);
     if (w.adv_h) (void)hipHostFree(w.adv_h);
     for (auto& r : w.retired) (void)hipFree(r.first);
     w.retired.clear();
-    w.ws = nullptr; w.ews = nullptr; w.aws = nullptr; w.hws = nullptr; w.hws_dev = nullptr;
+    w.ws = nullptr; w.ews = nullptr; w.tws = nullptr; w.aws = nullptr; w.hws = nullptr; w.hws_dev = nullptr;
     w.adv_h = nullptr; w.adv_d = nullptr;
-    w.ws_bytes = w.ews_bytes = w.aws_bytes = w.hws_bytes = 0;
+    w.ws_bytes = w.ews_bytes = w.tws_bytes = w.aws_bytes = w.hws_bytes = 0;
     w.aux_state_ok = false;
     w.stream = nullptr;
     w.capture = 0;
@@ -511,6 +514,14 @@ int WsSlot::encode_workspace(size_t bytes, void** out) {
     const int rc = grow(w, &w->ews, &w->ews_bytes, bytes, st, 0, "hipMalloc(encode workspace)");
     if (rc) return rc;
     *out = w->ews;
+    return 0;
+}
+
+int WsSlot::text_workspace(size_t bytes, void** out) {
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    const int rc = grow(w, &w->tws, &w->tws_bytes, bytes, st, 0, "hipMalloc(text workspace)");
+    if (rc) return rc;
+    *out = w->tws;
     return 0;
 }
 

@@ -330,6 +330,7 @@ struct WsSlot {
     void release();
     int workspace(size_t bytes, size_t zero_bytes, void** out);   // decode / reassembly / stream
     int encode_workspace(size_t bytes, void** out);
+    int text_workspace(size_t bytes, void** out);                  // the text validator (ws_utf8.hip)
     int aux(size_t dbytes, size_t hbytes, WsAux* out);
     int advice(int** host, int** dev);                             // the stride hint words (eager)
     int side(hipStream_t* side, hipEvent_t* ev, int prio);         // the raw stream's split walk: side stream + events

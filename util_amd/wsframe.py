@@ -25,6 +25,12 @@ SEG_OK, SEG_MAX_FRAMES, SEG_ERR_DECODE, SEG_ERR_LEN_WRAP = 0, 1, -1, -2
 SEG_ERR_OUT_SPACE = -3
 SEG_ERR_CACHE_OVERFLOW = -4
 REASM_CONTROL_DIRECT = 1  # WEBSOCKET_REASM_CONTROL_DIRECT: control frames delivered apart from fragmented messages
+# include/wsframe_amd_text.h: verdicts of batch_validate_text_device, its "no INVALID message" value and state bits
+TEXT_NA, TEXT_VALID, TEXT_INVALID = 0, 1, 2
+TEXT_NONE = 0xFFFFFFFF
+TEXT_ST_PENDING, TEXT_ST_FAILED = 0x80000000, 0x40000000
+# the validator's geometry (ws_utf8.hip): 16-B chunk per lane, 64 chunks per wave row, 4 rows per tile
+TEXT_CHUNK, TEXT_ROW, TEXT_TILE = 16, 1024, 4096
 NETPACKET_FRAGMENT = 6  # transport_ctx.h:11-18; the pktype websocketframeOnDecode reports
 DATA_OFF_NULL = 0xFFFFFFFFFFFFFFFF
 BATCH_PAD = 32  # WEBSOCKET_BATCH_PAD: readable device bytes required after every segment
@@ -189,6 +195,25 @@ def batch_reassemble_device(buf, seg_off, seg_len, max_frames, desc, res, out, m
         _ptr(out), _ptr(out_off), _ptr(msg), _ptr(nmsg), _ptr(open_state), int(readcache_max), _ptr(cached),
         _stream(stream))
     check(rc, "websocketframeBatchReassembleDeviceEx")
+
+
+def batch_validate_text_device(out, desc, msg, nmsg, max_frames, verdict, text_state=None, first_bad=None, stream=None):
+    """websocketframeBatchValidateTextDevice (libwsframe_amd_text.so) on what a reassembly call on
+    the same stream just produced: out (uint8), desc / msg (uint8 >= 32*nseg*max_frames), nmsg
+    (int32 nseg); verdict (int32 >= nseg*max_frames: TEXT_NA / TEXT_VALID / TEXT_INVALID at slot
+    s*max_frames + i, i < nmsg[s]; other slots are not written), text_state (int32 nseg, in/out,
+    optional: the per-connection carry, zero when the connection starts), first_bad (int32 nseg,
+    optional: the least i with TEXT_INVALID, else TEXT_NONE as u32); async on `stream`."""
+    nseg = nmsg.numel()
+    assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
+    assert msg.numel() * msg.element_size() >= 32 * nseg * max_frames
+    assert verdict.numel() * verdict.element_size() >= 4 * nseg * max_frames
+    assert text_state is None or text_state.numel() * text_state.element_size() >= 4 * nseg
+    assert first_bad is None or first_bad.numel() * first_bad.element_size() >= 4 * nseg
+    lib = _lib.load_text_lib()
+    rc = lib.websocketframeBatchValidateTextDevice(_ptr(out), _ptr(desc), _ptr(msg), _ptr(nmsg), nseg, max_frames,
+                                                   _ptr(text_state), _ptr(verdict), _ptr(first_bad), _stream(stream))
+    check(rc, "websocketframeBatchValidateTextDevice", lib)
 
 
 def batch_encode_device(src, frames, dst, wire_off, capacity=None, stream=None):
