@@ -545,3 +545,36 @@ def test_stream_split_captured(dev, split_opts, cap):
                                   od[:int(orr[0]["n_frames"])])
             assert np.array_equal(d[:n].cpu().numpy(), ob)
         del g
+
+
+def test_three_linkers_agree_on_a_small_stream(dev, split_opts):
+    """2 MiB of 0-300 B client frames, decoded with the chain linked by the host (stream_rw 2), by the
+    serial device linker (stream_plink 0) and by the parallel one (stream_plink 1): as generated, with
+    one unmasked frame near the middle (a dead owner walk), with one 200 KiB frame (chunks without an
+    entry), truncated, and stopped by max_frames at half the length. All three share one link rule
+    (ws_link.h); every call bit-exact vs the oracle"""
+    rng = np.random.default_rng(700)
+    wire = long_stream(rng, 2 << 20, lambda g: g.integers(0, 301), masked=1.0)
+    od, orr = oracle_segments(wire.copy(), [0], [len(wire)], 1 << 15)
+    fo = od["frame_off"][:int(orr[0]["n_frames"])]
+    mid = int(fo[np.searchsorted(fo, len(wire) // 2)])
+
+    def spliced(plen, masked):
+        h = bytes([0x82, (0x80 if masked else 0) | 127]) + plen.to_bytes(8, "big") if plen > 0xFFFF else \
+            bytes([0x82, (0x80 if masked else 0) | 126]) + plen.to_bytes(2, "big")
+        body = rng.integers(0, 256, (4 if masked else 0) + plen, dtype=np.uint8)
+        return np.concatenate([wire[:mid], np.frombuffer(h, dtype=np.uint8), body, wire[mid:]])
+
+    variants = [("plain", wire, 1 << 15), ("unmasked", spliced(200, False), 1 << 15),
+                ("long", spliced(200 << 10, True), 1 << 15), ("truncated", wire[:len(wire) - 999].copy(), 1 << 15),
+                ("max_frames", wire, int(np.searchsorted(fo, len(wire) // 2)))]
+    try:
+        for name, w, mf in variants:
+            for rw, plink in ((2, 1), (1, 0), (1, 1)):
+                W.set_option("stream_rw", rw)
+                W.set_option("stream_plink", plink)
+                run(dev, w, mf)
+                if name == "plain" and rw == 2:
+                    assert W.get_stat("stream_rw_chunks") >= 3 and W.get_stat("stream_rw_chunk_walks") == 0
+    finally:
+        W.set_option("stream_plink", 1)

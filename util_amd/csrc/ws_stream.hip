@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ws_common.h"
+#include "ws_link.h"
 
 #define SPASS_T 256
 
@@ -396,13 +397,8 @@ __global__ __launch_bounds__(64) void ws_rw_chunk_kernel(const unsigned char* __
 #define RW_HMAX (128u << 10)
 #define RW_HMIN (4u << 10)
 #define RW_SAMPLE (256ull << 10)
-#define RW_S0 40          // records per chunk of walks that leave it (~8-16 true frame starts)
-#define RW_S1 8           // ... of walks that end the stream in it
-#define RW_SLOTS (RW_S0 + RW_S1)
-#define RW_SLAST 4096     // walks that end the stream in the last chunk
-#define RW_MAXSTEPS 65536
+// (the record pools RW_S0, RW_S1, RW_SLAST, the owners per chunk RW_D: ws_link.h)
 #define RW_TPOS 64        // window positions per thread
-#define RW_D 4            // distinct window exits per chunk walked on (phase B owners)
 #define RW_STG 4096       // largest staging list per owner (frame offsets); the call's is stgn
 #define RW_MIN (512ull << 10)     // streams shorter than this after the passes: one wavefront walks
 #define RW_MIN_FRAMES 256         // ... and, after the sample, fewer frames than this (by the mean)
@@ -431,20 +427,6 @@ __device__ static u32 rw_window(u64 mean, u32 maxlen, u64 C) {
     h = (h + 4095) & ~4095ull;
     return (u32)(h < RW_HMIN ? RW_HMIN : (h > hi ? hi : h));
 }
-
-struct RwRec {            // phase A: one surviving walk from chunk start + start
-    u32 start;
-    u32 cs;               // frames consumed | status << 31 (0 left the window, 1 the stream's walk ends)
-    u64 exit;             // the next frame start (status 0) or where the walk ended
-};
-
-struct RwOwn {            // phase B: the walk from a window exit to the chunk's end
-    u64 exit;             // the next frame start (left the chunk) or where the stream's walk ends
-    u32 cs;               // frames | status << 31
-    u32 dead;             // 1: an implausible header (not the chain)
-    u64 over;             // the (stgn+1)-th frame's start when more than stgn frames
-    u64 pad;
-};
 
 // The walk's geometry chosen on the device (captured calls: the host cannot read the sample):
 // R1-R3, the linker and the emit take it from here; scratch is sized for the caps at capture.
@@ -493,23 +475,19 @@ __device__ __forceinline__ void rw_hand_over(RwPlan* plan, int part, u64 ent, u3
     plan->in_state[part + 1] = 1;
 }
 
-// a kernel's chunk grid: the plan's part (device-planned calls) or the host's arguments
+// a kernel's chunk grid: the plan's part (device-planned calls) or the host's (passed by value,
+// not looked at when the kernel has a plan)
 struct RwGeo {
     u64 P, C;
     u32 H, n, cbase, capc, stgn, nall, need_mask;
     u64 stg_base, cand_base;
 };
-__device__ __forceinline__ RwGeo rw_geo(const RwPlan* plan, int part, u64 P, u64 C, u32 H, u32 nchunks, u32 capc,
-                                        u32 stgn, u32 need_mask) {
+__device__ __forceinline__ RwGeo rw_geo(const RwPlan* plan, int part, const RwGeo& host) {
+    if (!plan) return host;
     RwGeo G;
-    if (plan) {
-        const RwPart& t = plan->pt[part];
-        G.P = t.P; G.C = t.C; G.H = t.H; G.n = t.n; G.cbase = t.cbase; G.capc = t.capc; G.stgn = t.stgn;
-        G.nall = plan->nchunks; G.need_mask = plan->need_mask; G.stg_base = t.stg_base; G.cand_base = t.cand_base;
-    } else {
-        G.P = P; G.C = C; G.H = H; G.n = nchunks; G.cbase = 0; G.capc = capc; G.stgn = stgn; G.nall = nchunks;
-        G.need_mask = need_mask; G.stg_base = 0; G.cand_base = 0;
-    }
+    const RwPart& t = plan->pt[part];
+    G.P = t.P; G.C = t.C; G.H = t.H; G.n = t.n; G.cbase = t.cbase; G.capc = t.capc; G.stgn = t.stgn;
+    G.nall = plan->nchunks; G.need_mask = plan->need_mask; G.stg_base = t.stg_base; G.cand_base = t.cand_base;
     return G;
 }
 
@@ -523,27 +501,6 @@ __device__ __forceinline__ void rw_note_max(const RwPlan* plan, u32 mx, u32 lane
     if (plan && lane == 0 && mx) atomicMax(const_cast<u32*>(&plan->seen_max), mx);
 }
 
-// b23: header bytes 2 and 3 (the top of a 64-bit length, which a real frame leaves zero:
-// a random 64-bit length reads as an incomplete frame and would crowd the records)
-__device__ __forceinline__ bool rw_plausible(u32 b0, u32 b1, u32 b23, bool need_mask) {
-    const u32 op = b0 & 15u;
-    return !(b0 & 0x70u) && (op <= 2u || (op >= 8u && op <= 10u)) && (!need_mask || (b1 & 0x80u)) &&
-           ((b1 & 0x7Fu) != 127u || b23 == 0u);
-}
-
-// One speculative step at pos: 0 frame (pos advanced), 1 the stream's walk ends at pos,
-// 2 implausible header (a wrong start)
-__device__ __forceinline__ u32 rw_step(uintptr_t origin, u64 len, u64& pos, bool need_mask) {
-    if (pos >= len || len - pos < 2) return 1;                               // websocketframe.c:121
-    u64 h0, h1;
-    ws_load16(origin + pos, h0, h1);
-    if (!rw_plausible((u32)h0 & 0xFFu, (u32)(h0 >> 8) & 0xFFu, (u32)(h0 >> 16) & 0xFFFFu, need_mask)) return 2;
-    const u32 fl = ws_plain_frame_len(ws_parse(h0, h1, len - pos));
-    if (!fl) return 1;
-    pos += fl;
-    return 0;
-}
-
 // R1 (candidates): one thread per RW_TPOS window positions (aligned 16-B loads); the
 // plausible positions of a wavefront are appended to its chunk's list (capc slots) with
 // one atomic per wave on the chunk's counter
@@ -551,13 +508,13 @@ __device__ __forceinline__ u32 rw_step(uintptr_t origin, u64 len, u64& pos, bool
 // A candidate whose frame is followed by an implausible header inside its chunk is dropped
 // here (R2 would drop it at that step: its second header), so the list holds only starts that
 // survive two headers (cfg3: R2 150 -> 24 us, R1 + R2 279 -> 154 us with the windows below)
-__global__ __launch_bounds__(256) void ws_rw_cand_kernel(const unsigned char* __restrict__ buf, u64 len, u64 P,
-                                                         u64 C, u32 H, u32 nchunks, u32 need_mask,
-                                                         u64* __restrict__ cand, u32* __restrict__ nrec, u32 capc,
+__global__ __launch_bounds__(256) void ws_rw_cand_kernel(const unsigned char* __restrict__ buf, u64 len, RwGeo hg,
+                                                         u64* __restrict__ cand, u32* __restrict__ nrec,
                                                          const RwPlan* __restrict__ plan, int part) {
     if (plan && !plan->active) return;
-    const RwGeo G = rw_geo(plan, part, P, C, H, nchunks, capc, 0, need_mask);   // geometry from the device
-    P = G.P; C = G.C; H = G.H; need_mask = G.need_mask; capc = G.capc;
+    const RwGeo G = rw_geo(plan, part, hg);                                  // geometry from the device
+    const u64 P = G.P, C = G.C;
+    const u32 H = G.H, need_mask = G.need_mask, capc = G.capc;
     const u32 lane = threadIdx.x & 63;
     __shared__ unsigned short s_cand[256 / 64][RW_WCAP];                     // a wave's candidates (position in its 4 KiB)
     const u32 per = H / RW_TPOS;                                             // a multiple of 64: one
@@ -665,16 +622,16 @@ __global__ __launch_bounds__(256) void ws_rw_cand_kernel(const unsigned char* __
 // R2 (window walks): one lane per candidate (grid-stride), the walk to the window's end
 // -> an A record {start, frames, exit_w}; a walk that left the window claims exit_w in
 // dx[] (one walk per distinct exit: merged walks share it) for R3
-__global__ __launch_bounds__(256) void ws_rw_spec_kernel(const unsigned char* __restrict__ buf, u64 len, u64 P,
-                                                         u64 C, u32 H, u32 nchunks, u32 need_mask,
-                                                         const u64* __restrict__ cand, u32 capc,
+__global__ __launch_bounds__(256) void ws_rw_spec_kernel(const unsigned char* __restrict__ buf, u64 len, RwGeo hg,
+                                                         const u64* __restrict__ cand,
                                                          RwRec* __restrict__ recs, u32* __restrict__ nrec,
                                                          unsigned long long* __restrict__ dx,
                                                          const RwPlan* __restrict__ plan, int part) {
     if (plan && !plan->active) return;
-    const RwGeo G = rw_geo(plan, part, P, C, H, nchunks, capc, 0, need_mask);
-    P = G.P; C = G.C; H = G.H; need_mask = G.need_mask; capc = G.capc;
-    nchunks = G.nall;                                                        // (the last chunk's pool)
+    const RwGeo G = rw_geo(plan, part, hg);
+    const u64 P = G.P, C = G.C;
+    const u32 H = G.H, need_mask = G.need_mask, capc = G.capc;
+    const u32 nchunks = G.nall;                                              // (the last chunk's pool)
     const uintptr_t origin = reinterpret_cast<uintptr_t>(buf);
     const u64 n = (u64)G.n * capc;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
@@ -696,16 +653,15 @@ __global__ __launch_bounds__(256) void ws_rw_spec_kernel(const unsigned char* __
             if (vr == 2) continue;
         }
         const u32 st = r;                                                    // 1: the walk ends in the window
-        // the last chunk's window lies near the stream's end, where wrong starts read as
-        // incomplete frames: its walks that end get a pool of their own
-        const bool lastc = c + 1 == nchunks;
+        // its slot in the chunk's pool of that kind (rw_pools: every slot of a pool, none counted yet)
+        const RwPools pl = rw_pools(c, nchunks, ~0u, ~0u);
         const u32 slot = atomicAdd(nrec + 4 * c + st, 1u);
-        if (slot < (st ? (lastc ? RW_SLAST : RW_S1) : RW_S0)) {
+        if (slot < (st ? pl.n1 : pl.n0)) {
             RwRec rr;
             rr.start = (u32)(start - cs0);
             rr.cs = cnt | (st << 31);
             rr.exit = pos;
-            recs[st && lastc ? (u64)nchunks * RW_SLOTS + slot : c * RW_SLOTS + (st ? RW_S0 : 0) + slot] = rr;
+            recs[(st ? pl.i1 : pl.i0) + slot] = rr;
         }
         if (st) continue;
         for (u32 d = 0; d < RW_D; ++d) {
@@ -718,14 +674,14 @@ __global__ __launch_bounds__(256) void ws_rw_spec_kernel(const unsigned char* __
 // R3 (chunk walks): one lane per claimed window exit, the walk to the chunk's end; the
 // offsets of the frames it passes go to the staging list (the emit writes them in parallel)
 #define RW_OWN_T 64       // one wavefront per block: the owner walks spread over every CU
-__global__ __launch_bounds__(RW_OWN_T) void ws_rw_own_kernel(const unsigned char* __restrict__ buf, u64 len, u64 P, u64 C,
-                                                        u32 nchunks, u32 need_mask,
+__global__ __launch_bounds__(RW_OWN_T) void ws_rw_own_kernel(const unsigned char* __restrict__ buf, u64 len, RwGeo hg,
                                                         const unsigned long long* __restrict__ dx,
-                                                        RwOwn* __restrict__ own, u32* __restrict__ stg, u32 stgn,
+                                                        RwOwn* __restrict__ own, u32* __restrict__ stg,
                                                         const RwPlan* __restrict__ plan, int part) {
     if (plan && !plan->active) return;
-    const RwGeo G = rw_geo(plan, part, P, C, 0, nchunks, 0, stgn, need_mask);
-    P = G.P; C = G.C; need_mask = G.need_mask; stgn = G.stgn;
+    const RwGeo G = rw_geo(plan, part, hg);
+    const u64 P = G.P, C = G.C;
+    const u32 need_mask = G.need_mask, stgn = G.stgn;
     const u64 ol = (u64)blockIdx.x * RW_OWN_T + threadIdx.x;                 // local owner index
     if (ol >= (u64)G.n * RW_D) return;
     const u64 oi = (u64)G.cbase * RW_D + ol;                                 // global
@@ -752,13 +708,13 @@ __global__ __launch_bounds__(RW_OWN_T) void ws_rw_own_kernel(const unsigned char
     own[oi] = ow;
 }
 
-// emit: one wavefront per chain chunk, tab[b] = {entry, exit_w, nf0, cnt_w, owner, n_par,
-// last, cs0}: the window prefix [entry, exit_w) by the group walk, then n_par staged
+// emit: one wavefront per chain chunk, tab[b] its row (RwRow, ws_link.h): the window prefix
+// [ent, exit_w) by the group walk, then n_par staged
 // frames in parallel (lane i: frame i, i + 64, ...), then the group walk from the next
 // frame to the chunk's exit (or, last, to the stream's end: tail, count, result).
 // owner == ~0: the whole rest from entry by the group walk (a chain ending in the window).
 __global__ __launch_bounds__(64) void ws_rw_emit_kernel(const unsigned char* __restrict__ buf, u64 len, u32 max_frames,
-                                                        const u64* __restrict__ tab, const RwOwn* __restrict__ own,
+                                                        const RwRow* __restrict__ tab, const RwOwn* __restrict__ own,
                                                         const u32* __restrict__ stg, u32 stgn,
                                                         WebsocketFrameDesc_t* __restrict__ desc,
                                                         u32x4* __restrict__ items, u64* __restrict__ ptr, u64 pend,
@@ -773,9 +729,9 @@ __global__ __launch_bounds__(64) void ws_rw_emit_kernel(const unsigned char* __r
         obase = (u64)pt.cbase * RW_D;
         sbase = pt.stg_base;
     }
-    const u64* t = tab + 8 * row;
-    const u64 ent = t[0], exit_w = t[1], nf0 = t[2], cnt_w = t[3], oi = t[4], n_par = t[5], cs0 = t[7];
-    const bool last = t[6] != 0;
+    const RwRow t = tab[row];
+    const u64 ent = t.ent, exit_w = t.exit_w, nf0 = t.nf0, cnt_w = t.cnt_w, oi = t.owner, n_par = t.n_par, cs0 = t.cs0;
+    const bool last = t.last != 0;
     const u32 lane = threadIdx.x;
     // the row that ends the walk also writes the count K2's launches from this part on read
     auto note_end = [&](const SwOut& o) {
@@ -973,8 +929,8 @@ __global__ __launch_bounds__(64) void ws_rw_plan_kernel(const unsigned char* __r
 // agree on ONE exit, and then the entry into chunk c is known without the chain before it.
 // ws_rw_plink_kernel (one wavefront per chunk): entry = that common exit (chunk 0: the
 // plan's P), its record, its owner; ws_rw_pscan_kernel (one block): the frame counts'
-// prefix sum up to the first chunk that ends the walk, and the emit rows exactly as the
-// serial linker writes them. Anything else — live owners that disagree, an entry outside
+// prefix sum up to the first chunk that ends the walk, and the emit rows by the rule the
+// serial linker takes them from (rw_link_decide, ws_link.h). Anything else — live owners that disagree, an entry outside
 // its window or without a record or owner, a frame spanning a whole chunk, max_frames
 // reached before the chain's last chunk, no chunk ending the walk — leaves nrows at 0 and
 // the serial linker runs.
@@ -998,10 +954,6 @@ __global__ __launch_bounds__(64) void ws_rw_plink_kernel(u64 len, const RwPlan* 
     const bool lastc = c + 1 == nchunks;
     // the next chunk's size (a part's last chunk: the next part's first)
     const u64 Cn = (cl + 1 == pt.n && part + 1 < (int)plan->nparts) ? plan->pt[part + 1].C : C;
-    auto rl64 = [](u64 v, int i) -> u64 {
-        return (u64)(u32)__builtin_amdgcn_readlane((int)(u32)v, i) |
-               ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), i) << 32);
-    };
     // the entry: the common exit of chunk c-1's live owners; a part's first chunk: the part's
     // origin (part 0) or the previous part's hand-off (the chain's exact entry)
     u64 ent = part == 0 ? P : plan->in_ent[part];
@@ -1015,62 +967,33 @@ __global__ __launch_bounds__(64) void ws_rw_plink_kernel(u64 len, const RwPlan* 
         if (!m) {
             ok = false;
         } else {
-            ent = rl64(o.exit, __builtin_ctzll(m));
+            ent = rw_readlane64(o.exit, __builtin_ctzll(m));
             ok = __ballot(live && o.exit != ent) == 0;
         }
     }
     ok = ok && ent >= cs0 && ent - cs0 < H && (lastc || ent - cs0 < C);
     RwLink L = {ent, 0, 0, 0, 0, 0};
     if (ok) {
-        const u32 so = (u32)(ent - cs0);
-        const u32 n0 = nrec[4 * c], n1 = nrec[4 * c + 1];
-        const u32 na = n0 < RW_S0 ? n0 : RW_S0;
-        const RwRec q = recs[c * RW_SLOTS + (lane < RW_S0 ? lane : 0)];
-        u64 m = __ballot(lane < na && q.start == so);
-        u32 rcs = 0;
-        u64 rexit = 0;
-        bool found = false;
-        if (m) {
-            const int i = __builtin_ctzll(m);
-            rcs = (u32)__builtin_amdgcn_readlane((int)q.cs, i);
-            rexit = rl64(q.exit, i);
-            found = true;
-        } else {                                                             // walks that end the stream
-            const RwRec* r1 = lastc ? recs + (u64)nchunks * RW_SLOTS : recs + c * RW_SLOTS + RW_S0;
-            const u32 nb1 = lastc ? (n1 < RW_SLAST ? n1 : RW_SLAST) : (n1 < RW_S1 ? n1 : RW_S1);
-            for (u32 k0 = 0; k0 < nb1 && !found; k0 += 64) {
-                RwRec q1 = {};
-                if (k0 + lane < nb1) q1 = r1[k0 + lane];
-                const u64 m1 = __ballot(k0 + lane < nb1 && q1.start == so);
-                if (m1) {
-                    const int i = __builtin_ctzll(m1);
-                    rcs = (u32)__builtin_amdgcn_readlane((int)q1.cs, i);
-                    rexit = rl64(q1.exit, i);
-                    found = true;
-                }
-            }
-        }
-        if (found) {
-            L.cnt_w = rcs & 0x7FFFFFFFu;
-            L.rexit = rexit;
-            if (rcs >> 31) {
+        const RwPools pl = rw_pools(c, nchunks, nrec[4 * c], nrec[4 * c + 1]);
+        const RwRec q = recs[pl.i0 + (lane < RW_S0 ? lane : 0)];
+        const RwHit r = rw_wave_find_rec(q, recs, pl, (u32)(ent - cs0), lane);
+        if (r.found) {
+            L.cnt_w = r.cs & 0x7FFFFFFFu;
+            L.rexit = r.exit;
+            if (r.cs >> 31) {
                 L.flags = 1 | 2 | 4;                                         // the walk ends in the window
             } else {
                 const u64 oi = c * RW_D + (lane & (RW_D - 1));
-                const u64 d = dx[oi];
-                const RwOwn o = own[oi];
-                const u64 mo = __ballot(lane < RW_D && d == rexit);
-                if (mo) {
-                    const int i = __builtin_ctzll(mo);
-                    const u32 dead = (u32)__builtin_amdgcn_readlane((int)o.dead, i);
-                    const u32 ocs = (u32)__builtin_amdgcn_readlane((int)o.cs, i);
-                    const u64 oexit = rl64(o.exit, i);
-                    const bool ends = (ocs >> 31) != 0 || oexit >= len;
-                    if (!dead && (ends || (oexit >= cs0 + C && oexit - (cs0 + C) < Cn && !lastc))) {
-                        L.nb = ocs & 0x7FFFFFFFu;
-                        L.oi = (u32)(c * RW_D + (u64)i);
-                        L.flags = 1 | (ends ? 4 : 0);
-                    }
+                const unsigned long long d = dx[oi];
+                const RwOwn w = own[oi];
+                const RwOwnHit o = rw_wave_find_own(d, w, c, r.exit, lane);
+                if (o.oi != ~0ull && !o.dead) {
+                    L.nb = o.cs & 0x7FFFFFFFu;                               // (both looked at only with flag 1)
+                    L.oi = (u32)o.oi;
+                    // (narrower than rw_link_decide's owner: an exit that skips the next chunk is left to
+                    // the serial linker, whose chain this chunk's successor then is not part of)
+                    const bool ends = rw_own_ends(o.cs, o.exit, len);
+                    if (ends || (o.exit >= cs0 + C && o.exit - (cs0 + C) < Cn && !lastc)) L.flags = 1 | (ends ? 4 : 0);
                 }
             }
         }
@@ -1080,8 +1003,8 @@ __global__ __launch_bounds__(64) void ws_rw_plink_kernel(u64 len, const RwPlan* 
 
 // one block of RW_PS_T threads: the prefix sum of the chain's frame counts and the emit rows
 #define RW_PS_T 1024
-__global__ __launch_bounds__(RW_PS_T) void ws_rw_pscan_kernel(u32 max_frames, RwPlan* __restrict__ plan,
-                                                             const RwLink* __restrict__ lk, u64* __restrict__ tab,
+__global__ __launch_bounds__(RW_PS_T) void ws_rw_pscan_kernel(u64 len, u32 max_frames, RwPlan* __restrict__ plan,
+                                                             const RwLink* __restrict__ lk, RwRow* __restrict__ tab,
                                                              const RwOwn* __restrict__ own, int part) {
     __shared__ u32 s_stop;
     __shared__ u32 s_bad;
@@ -1121,22 +1044,14 @@ __global__ __launch_bounds__(RW_PS_T) void ws_rw_pscan_kernel(u32 max_frames, Rw
         for (u32 w = 0; w < wv; ++w) before += s_wsum[w];
         const u64 nfc = before + x - cnt;
         const u64 cs0 = pt.P + (u64)c * pt.C;
-        if (c < stop) {
-            if (nfc + cnt >= max_frames) s_bad = 1;                         // max_frames mid-chain: serial
-            u64* t = tab + 8 * ((u64)cb + c);
-            const u64 n_par = L.nb < stgn ? L.nb : stgn;
-            t[0] = L.ent; t[1] = L.rexit; t[2] = nfc; t[3] = L.cnt_w; t[4] = L.oi; t[5] = n_par; t[6] = 0;
-            t[7] = cs0;
-        } else if (c == stop && stop < n) {
-            u64* t = tab + 8 * ((u64)cb + c);
-            if ((L.flags & 2) || nfc + L.cnt_w >= max_frames) {             // ends in the window: group walk
-                t[0] = L.ent; t[1] = 0; t[2] = nfc; t[3] = 0; t[4] = ~0ull; t[5] = 0; t[6] = 1; t[7] = cs0;
-            } else {
-                u64 n_par = L.nb < stgn ? L.nb : stgn;
-                if (nfc + L.cnt_w + n_par > max_frames) n_par = max_frames - nfc - L.cnt_w;
-                t[0] = L.ent; t[1] = L.rexit; t[2] = nfc; t[3] = L.cnt_w; t[4] = L.oi; t[5] = n_par; t[6] = 1;
-                t[7] = cs0;
-            }
+        if (c <= stop && c < n) {
+            // the link as plink found it: flag 2 is the record's status bit, flag 4 an owner walk that ends
+            // the chain (rw_own_ends, said here by an exit at the stream's end; the exit itself is not kept)
+            const RwHit r = {true, L.cnt_w | ((L.flags & 2) ? 1u << 31 : 0u), L.rexit};
+            const RwOwnHit o = {(u64)L.oi, L.nb, 0u, (L.flags & 4) ? len : 0ull};
+            const RwLinkOut d = rw_link_decide(L.ent, cs0, nfc, r, o, stgn, max_frames, len);
+            if (c < stop && d.last) s_bad = 1;                              // max_frames mid-chain: serial
+            tab[(u64)cb + c] = d.row;
         }
         __syncthreads();
         if (tid == RW_PS_T - 1) s_carry = before + x;
@@ -1166,7 +1081,7 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
                                                         RwPlan* __restrict__ plan, const RwRec* __restrict__ recs,
                                                         const u32* __restrict__ nrec,
                                                         const unsigned long long* __restrict__ dx,
-                                                        const RwOwn* __restrict__ own, u64* __restrict__ tab,
+                                                        const RwOwn* __restrict__ own, RwRow* __restrict__ tab,
                                                         WebsocketFrameDesc_t* __restrict__ desc,
                                                         u32x4* __restrict__ items, u64* __restrict__ ptr, u64 pend,
                                                         u32* __restrict__ nwork, WebsocketSegResult_t* __restrict__ res,
@@ -1184,13 +1099,6 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
     bool last = false;
     u32 cnt_end = 0;                                                         // the count a finishing walk wrote
     bool ended_walk = false;
-    auto row = [&](u64 a0, u64 a1, u64 a2, u64 a3, u64 a4, u64 a5, u64 a6, u64 a7) {
-        if (lane == 0) {
-            u64* t = tab + 8 * ((u64)cb + rows);
-            t[0] = a0; t[1] = a1; t[2] = a2; t[3] = a3; t[4] = a4; t[5] = a5; t[6] = a6; t[7] = a7;
-        }
-        ++rows;
-    };
     // The records of RW_LK consecutive chunks are loaded in one round (the chain almost always
     // moves to the next chunk), then taken one chunk at a time; a chain that leaves that run
     // (a skipped chunk, a chunk walked here) reloads at its new chunk.
@@ -1223,67 +1131,25 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
             const u64 c = (ent - P) / C, cs0 = P + c * C;                    // local chunk
             if (c != c0 + k) break;                                          // left the run: reload
             ++steps;
-            bool found = false;
-            RwRec r = {};
             const u64 gcx = (u64)cb + c;                                     // global chunk
+            RwHit r = {false, 0u, 0ull};
             if (c < np && ent - cs0 < H) {
-                const u32 so = (u32)(ent - cs0);
-                const bool lastc = gcx + 1 == nchunks;
-                const u32 n0k = (u32)__builtin_amdgcn_readlane((int)n0v, (int)k);
-                const u32 n1k = (u32)__builtin_amdgcn_readlane((int)n1v, (int)k);
-                const u32 na = n0k < RW_S0 ? n0k : RW_S0;
-                const u64 m = __ballot(lane < na && q[k].start == so);
-                if (m) {
-                    const int i = __builtin_ctzll(m);
-                    r.start = so;
-                    r.cs = (u32)__builtin_amdgcn_readlane((int)q[k].cs, i);
-                    r.exit = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)q[k].exit, i)) |
-                             ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(q[k].exit >> 32), i) << 32);
-                    found = true;
-                } else {                                                     // walks that end the stream
-                    const RwRec* r1 = lastc ? recs + (u64)nchunks * RW_SLOTS : recs + gcx * RW_SLOTS + RW_S0;
-                    const u32 nb1 = lastc ? (n1k < RW_SLAST ? n1k : RW_SLAST) : (n1k < RW_S1 ? n1k : RW_S1);
-                    for (u32 k0 = 0; k0 < nb1 && !found; k0 += 64) {
-                        RwRec q1 = {};
-                        if (k0 + lane < nb1) q1 = r1[k0 + lane];
-                        const u64 m1 = __ballot(k0 + lane < nb1 && q1.start == so);
-                        if (m1) {
-                            const int i = __builtin_ctzll(m1);
-                            r.start = so;
-                            r.cs = (u32)__builtin_amdgcn_readlane((int)q1.cs, i);
-                            r.exit = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)q1.exit, i)) |
-                                     ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(q1.exit >> 32), i) << 32);
-                            found = true;
-                        }
-                    }
-                }
+                const RwPools pl = rw_pools(gcx, nchunks, (u32)__builtin_amdgcn_readlane((int)n0v, (int)k),
+                                            (u32)__builtin_amdgcn_readlane((int)n1v, (int)k));
+                r = rw_wave_find_rec(q[k], recs, pl, (u32)(ent - cs0), lane);
             }
-            const u32 cnt_w = found ? (r.cs & 0x7FFFFFFFu) : 0u;
-            if (found && ((r.cs >> 31) || (u64)nfc + cnt_w >= max_frames)) { // ends in the window: group walk
-                row(ent, 0, nfc, 0, ~0ull, 0, 1, cs0);
-                last = true;
-                break;
-            }
-            if (found) {
-                // the owner walk of this exit (at most RW_D distinct exits per chunk)
-                const u64 mo = __ballot(lane < RW_D && dd[k] == r.exit);
-                if (mo) {
-                    const int i = __builtin_ctzll(mo);
-                    const u32 dead = (u32)__builtin_amdgcn_readlane((int)oo[k].dead, i);
-                    if (!dead) {
-                        const u32 ocs = (u32)__builtin_amdgcn_readlane((int)oo[k].cs, i);
-                        const u64 oexit = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)oo[k].exit, i)) |
-                                          ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(oo[k].exit >> 32), i) << 32);
-                        const u32 nb = ocs & 0x7FFFFFFFu;
-                        last = (ocs >> 31) != 0 || oexit >= len || (u64)nfc + cnt_w + nb >= max_frames;
-                        u64 n_par = nb < stgn ? nb : stgn;
-                        if (last && (u64)nfc + cnt_w + n_par > max_frames) n_par = max_frames - nfc - cnt_w;
-                        row(ent, r.exit, nfc, cnt_w, gcx * RW_D + (u64)i, n_par, last ? 1ull : 0ull, cs0);
-                        nfc += cnt_w + nb;
-                        ent = oexit;
-                        continue;
-                    }
-                }
+            // the owner walk of its exit (at most RW_D distinct exits per chunk), and what both mean
+            RwOwnHit ow = {~0ull, 0u, 0u, 0ull};
+            if (r.found) ow = rw_wave_find_own(dd[k], oo[k], gcx, r.exit, lane);
+            const RwLinkOut d = rw_link_decide(ent, cs0, nfc, r, ow, stgn, max_frames, len);
+            if (d.kind != RW_LINK_WALK) {
+                if (lane == 0) tab[(u64)cb + rows] = d.row;
+                ++rows;
+                last = d.last;
+                if (d.kind == RW_LINK_GROUP) break;
+                nfc = (u32)d.nfc;
+                ent = d.ent;
+                continue;
             }
             // no usable record: this wavefront walks the chunk (writing its frames)
             const SwOut o = stream_walk(buf, len, ent, 0, nfc, cs0 + C < len ? cs0 + C : len, false, max_frames, desc,
@@ -1420,7 +1286,7 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     const size_t b_nrec = ((size_t)nchunks * 16 + 255) & ~(size_t)255;     // per chunk: n0, n1, candidates
     const size_t b_dx = ((size_t)nchunks * RW_D * 8 + 255) & ~(size_t)255;
     const size_t b_own = ((size_t)nchunks * RW_D * sizeof(RwOwn) + 255) & ~(size_t)255;
-    const size_t b_tab = ((size_t)nchunks * 64 + 255) & ~(size_t)255;
+    const size_t b_tab = ((size_t)nchunks * sizeof(RwRow) + 255) & ~(size_t)255;
     // staging: about twice the chunk's mean frame count (frames past it are walked by the emit)
     const u32 stgn = (u32)rw_pow2_clamp(2 * C / (mean ? mean : 1), 256, RW_STG);
     const size_t b_stg = (size_t)nchunks * RW_D * stgn * 4;
@@ -1436,7 +1302,7 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     u32* nrec = reinterpret_cast<u32*>(w + 256 + b_recs);
     unsigned long long* dx = reinterpret_cast<unsigned long long*>(w + 256 + b_recs + b_nrec);
     RwOwn* own = reinterpret_cast<RwOwn*>(w + 256 + b_recs + b_nrec + b_dx + 256);
-    u64* tab = reinterpret_cast<u64*>(w + 256 + b_host);
+    RwRow* tab = reinterpret_cast<RwRow*>(w + 256 + b_host);
     u32* stg = reinterpret_cast<u32*>(w + 256 + b_host + b_tab);
     u64* cand = reinterpret_cast<u64*>(w + 256 + b_host + b_tab + b_stg);
     const RwRec* hr = reinterpret_cast<const RwRec*>(hw + 256);
@@ -1452,24 +1318,27 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
         return ws_set_err("stream walk setup", e);
     const u32 need_mask = (hb[1] & 0x80u) ? 1u : 0u;
     const u64 threads = nchunks * (H / RW_TPOS);
-    hipLaunchKernelGGL(ws_rw_cand_kernel, dim3((u32)((threads + 255) / 256)), dim3(256), 0, st, d_buf, len, P, C, H,
-                       (u32)nchunks, need_mask, cand, nrec, capc, (const RwPlan*)nullptr, 0);
+    RwGeo G;                                                                 // one part: the whole rest
+    G.P = P; G.C = C; G.H = H; G.n = (u32)nchunks; G.cbase = 0; G.capc = capc; G.stgn = stgn; G.nall = (u32)nchunks;
+    G.need_mask = need_mask; G.stg_base = 0; G.cand_base = 0;
+    hipLaunchKernelGGL(ws_rw_cand_kernel, dim3((u32)((threads + 255) / 256)), dim3(256), 0, st, d_buf, len, G, cand,
+                       nrec, (const RwPlan*)nullptr, 0);
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_rw_cand_kernel launch", e);
     const u32 r2_blocks = (u32)std::min<u64>((nchunks * capc + 255) / 256, 4096);  // grid-stride
-    hipLaunchKernelGGL(ws_rw_spec_kernel, dim3(r2_blocks), dim3(256), 0, st, d_buf, len, P, C, H, (u32)nchunks,
-                       need_mask, cand, capc, recs, nrec, dx, (const RwPlan*)nullptr, 0);
+    hipLaunchKernelGGL(ws_rw_spec_kernel, dim3(r2_blocks), dim3(256), 0, st, d_buf, len, G, cand, recs, nrec, dx,
+                       (const RwPlan*)nullptr, 0);
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_rw_spec_kernel launch", e);
-    hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((nchunks * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0, st, d_buf, len, P,
-                       C, (u32)nchunks, need_mask, dx, own, stg, stgn, (const RwPlan*)nullptr, 0);
+    hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((nchunks * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0, st,
+                       d_buf, len, G, dx, own, stg, (const RwPlan*)nullptr, 0);
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_rw_own_kernel launch", e);
     if ((e = hipMemcpyAsync(hw + 256, w + 256, b_host, hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return ws_set_err("stream walk records", e);
     // follow the chain from P: exact, every record is the reference loop from its start
-    std::vector<u64> ht;
+    std::vector<RwRow> ht;
     u64 ent = P;
     u32 nfc = nf;
-    ht.reserve(nchunks * 8 + 8);
+    ht.reserve(nchunks + 1);
     for (bool last = false; !last;) {
         const u64 c = (ent - P) / C, cs0 = P + c * C;
         if (c + 3 < nchunks) {                                               // the chain is sequential:
@@ -1480,40 +1349,17 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
             __builtin_prefetch(hown + cp * RW_D);
             __builtin_prefetch(hown + cp * RW_D + 2);
         }
-        const RwRec* r = nullptr;
-        if (c < nchunks && ent - cs0 < H) {
-            const u32 so = (u32)(ent - cs0);
-            for (u32 k = 0; k < hn[4 * c] && k < RW_S0; ++k)
-                if (hr[c * RW_SLOTS + k].start == so) { r = &hr[c * RW_SLOTS + k]; break; }
-            const bool lastc = c + 1 == nchunks;
-            const RwRec* r1 = lastc ? hr + nchunks * RW_SLOTS : hr + c * RW_SLOTS + RW_S0;
-            for (u32 k = 0; !r && k < hn[4 * c + 1] && k < (lastc ? RW_SLAST : RW_S1); ++k)
-                if (r1[k].start == so) { r = &r1[k]; break; }
-        }
-        const RwOwn* ow = nullptr;
-        u64 oi = ~0ull;
-        if (r && !(r->cs >> 31))
-            for (u32 d = 0; d < RW_D; ++d)
-                if (hdx[c * RW_D + d] == r->exit) {
-                    oi = c * RW_D + d;
-                    ow = hown[oi].dead ? nullptr : &hown[oi];
-                    break;
-                }
-        const u32 cnt_w = r ? (r->cs & 0x7FFFFFFFu) : 0u;
-        if (r && ((r->cs >> 31) || (u64)nfc + cnt_w >= max_frames)) {      // ends in the window: group walk
-            const u64 row[8] = {ent, 0, nfc, 0, ~0ull, 0, 1, cs0};
-            ht.insert(ht.end(), row, row + 8);
-            break;
-        }
-        if (ow) {
-            const u32 nb = ow->cs & 0x7FFFFFFFu;
-            last = (ow->cs >> 31) != 0 || ow->exit >= len || (u64)nfc + cnt_w + nb >= max_frames;
-            u64 n_par = nb < stgn ? nb : stgn;
-            if (last && (u64)nfc + cnt_w + n_par > max_frames) n_par = max_frames - nfc - cnt_w;
-            const u64 row[8] = {ent, r->exit, nfc, cnt_w, oi, n_par, last ? 1ull : 0ull, cs0};
-            ht.insert(ht.end(), row, row + 8);
-            nfc += cnt_w + nb;
-            ent = ow->exit;
+        RwHit r = {false, 0u, 0ull};
+        if (c < nchunks && ent - cs0 < H)
+            r = rw_find_rec(hr, rw_pools(c, nchunks, hn[4 * c], hn[4 * c + 1]), (u32)(ent - cs0));
+        RwOwnHit ow = {~0ull, 0u, 0u, 0ull};
+        if (r.found) ow = rw_find_own(hdx, hown, c, r.exit);
+        const RwLinkOut d = rw_link_decide(ent, cs0, nfc, r, ow, stgn, max_frames, len);
+        if (d.kind != RW_LINK_WALK) {
+            ht.push_back(d.row);
+            last = d.last;
+            ent = d.ent;
+            nfc = (u32)d.nfc;
             continue;
         }
         u64 nx = 0;
@@ -1523,10 +1369,10 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
         ent = nx;
         nfc = nfn;
     }
-    const u32 nblk = (u32)(ht.size() / 8);
+    const u32 nblk = (u32)ht.size();
     ws_stat_rw_chunks = nblk;
     if (nblk) {
-        if ((e = hipMemcpyAsync(tab, ht.data(), ht.size() * 8, hipMemcpyHostToDevice, st)) != hipSuccess)
+        if ((e = hipMemcpyAsync(tab, ht.data(), ht.size() * sizeof(RwRow), hipMemcpyHostToDevice, st)) != hipSuccess)
             return ws_set_err("hipMemcpyAsync(stream chain)", e);
         hipLaunchKernelGGL(ws_rw_emit_kernel, dim3(nblk), dim3(64), 0, st, d_buf, len, max_frames, tab, own, stg, stgn,
                            d_desc, Pw.items, Pw.ptr, Pw.npieces, Pw.nwork, d_res, (RwPlan*)nullptr, 0);
@@ -1558,7 +1404,7 @@ static RwDevLayout rw_dev_layout(u64 len) {
     L.zero_bytes = o - L.o_nrec;
     L.o_recs = o; o += up((L.nch_cap * RW_SLOTS + RW_SLAST) * sizeof(RwRec));
     L.o_own = o; o += up(L.nch_cap * RW_D * sizeof(RwOwn));
-    L.o_tab = o; o += up((L.nch_cap + 2) * 64);
+    L.o_tab = o; o += up((L.nch_cap + 2) * sizeof(RwRow));
     L.o_stg = o; o += up(L.stg_cap * 4);
     L.o_cand = o; o += up(L.cand_cap * 8);
     L.o_lk = o; o += up(L.nch_cap * sizeof(RwLink));
@@ -1590,7 +1436,7 @@ static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, Websock
     unsigned long long* dx = reinterpret_cast<unsigned long long*>(w + L.o_dx);
     RwRec* recs = reinterpret_cast<RwRec*>(w + L.o_recs);
     RwOwn* own = reinterpret_cast<RwOwn*>(w + L.o_own);
-    u64* tab = reinterpret_cast<u64*>(w + L.o_tab);
+    RwRow* tab = reinterpret_cast<RwRow*>(w + L.o_tab);
     u32* stg = reinterpret_cast<u32*>(w + L.o_stg);
     u64* cand = reinterpret_cast<u64*>(w + L.o_cand);
     RwLink* lk = reinterpret_cast<RwLink*>(w + L.o_lk);
@@ -1609,27 +1455,26 @@ static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, Websock
     // one part's candidate, window and owner walks; its linking and emit
     auto rwalk = [&](hipStream_t s, int part) {
         // R1 and R2 grid-stride, R3 one lane per (chunk, exit): grids for the caps
-        hipLaunchKernelGGL(ws_rw_cand_kernel, dim3(RW_R1_GRID), dim3(256), 0, s, d_buf, len, (u64)0, (u64)1, (u32)64, 0u,
-                           0u, cand, nrec, 0u, (const RwPlan*)plan, part);
-        hipLaunchKernelGGL(ws_rw_spec_kernel, dim3(RW_R2_GRID), dim3(256), 0, s, d_buf, len, (u64)0, (u64)1, (u32)64, 0u,
-                           0u, (const u64*)cand, 0u, recs, nrec, dx, (const RwPlan*)plan, part);
-        hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((L.nch_cap * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0,
-                           s, d_buf, len, (u64)0, (u64)1, 0u, 0u, (const unsigned long long*)dx, own, stg, 0u,
+        hipLaunchKernelGGL(ws_rw_cand_kernel, dim3(RW_R1_GRID), dim3(256), 0, s, d_buf, len, RwGeo{}, cand, nrec,
                            (const RwPlan*)plan, part);
+        hipLaunchKernelGGL(ws_rw_spec_kernel, dim3(RW_R2_GRID), dim3(256), 0, s, d_buf, len, RwGeo{}, (const u64*)cand,
+                           recs, nrec, dx, (const RwPlan*)plan, part);
+        hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((L.nch_cap * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0,
+                           s, d_buf, len, RwGeo{}, (const unsigned long long*)dx, own, stg, (const RwPlan*)plan, part);
     };
     auto rlink = [&](hipStream_t s, int part) {
         if (ws_stream_plink) {      // the chunk-parallel linker; the serial one below exits if it linked
             hipLaunchKernelGGL(ws_rw_plink_kernel, dim3((u32)L.nch_cap), dim3(64), 0, s, len, (const RwPlan*)plan,
                                (const RwRec*)recs, (const u32*)nrec, (const unsigned long long*)dx, (const RwOwn*)own,
                                lk, part);
-            hipLaunchKernelGGL(ws_rw_pscan_kernel, dim3(1), dim3(RW_PS_T), 0, s, max_frames, plan, (const RwLink*)lk, tab,
+            hipLaunchKernelGGL(ws_rw_pscan_kernel, dim3(1), dim3(RW_PS_T), 0, s, len, max_frames, plan, (const RwLink*)lk, tab,
                                (const RwOwn*)own, part);
         }
         hipLaunchKernelGGL(ws_rw_link_kernel, dim3(1), dim3(64), 0, s, d_buf, len, max_frames, plan, (const RwRec*)recs,
                            (const u32*)nrec, (const unsigned long long*)dx, (const RwOwn*)own, tab, d_desc, Pw.items,
                            Pw.ptr, Pw.npieces, Pw.nwork, d_res, part);
         hipLaunchKernelGGL(ws_rw_emit_kernel, dim3((u32)(L.nch_cap + 2)), dim3(64), 0, s, d_buf, len, max_frames,
-                           (const u64*)tab, (const RwOwn*)own, (const u32*)stg, 0u, d_desc, Pw.items, Pw.ptr,
+                           (const RwRow*)tab, (const RwOwn*)own, (const u32*)stg, 0u, d_desc, Pw.items, Pw.ptr,
                            Pw.npieces, Pw.nwork, d_res, plan, part);
     };
     if (!split) {
