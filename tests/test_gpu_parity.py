@@ -209,17 +209,58 @@ def test_synth_matches_numpy_generator(dev):
         assert np.array_equal(d.cpu().numpy(), wire)
 
 
+def generator_headers(wl):
+    """the generator's header bytes of every frame of a workload, one row of 14 per frame (bytes
+    past the header's length zero) and the header lengths: vectorised from plen_h and
+    util_amd/synth.py (b0 and key as tests/wsynth.py states them)"""
+    n = wl.nframes
+    plen = wl.plen_h.astype(np.uint64)
+    f = np.arange(wl.first_frame, wl.first_frame + n, dtype=np.uint64)
+    key = wsynth.keys(wl.seed, f).astype(np.uint64)
+    hl = (wl.wirelen_h - plen).astype(np.int64)
+    rows = np.zeros((n, 14), np.uint8)
+    rows[:, 0] = wsynth.b0s(wl.b0_kind, wl.first_frame + n)[wl.first_frame:]
+    small, mid, big = plen < 126, (plen >= 126) & (plen <= 0xFFFF), plen > 0xFFFF
+    rows[small, 1] = 0x80 | plen[small]
+    rows[mid, 1] = 0x80 | 126
+    rows[mid, 2], rows[mid, 3] = plen[mid] >> np.uint64(8), plen[mid] & np.uint64(0xFF)
+    rows[big, 1] = 0x80 | 127
+    for i in range(8):
+        rows[big, 2 + i] = (plen[big] >> np.uint64(56 - 8 * i)) & np.uint64(0xFF)
+    for cls, at in ((small, 2), (mid, 4), (big, 10)):
+        for i in range(4):
+            rows[cls, at + i] = (key[cls] >> np.uint64(8 * i)) & np.uint64(0xFF)
+    return rows, hl
+
+
+def assert_headers(wl, rows, hl, step=1 << 20):
+    """every frame's header bytes on the device equal the generator's (gathered with torch)"""
+    col = torch.arange(14, device=wl.dev)
+    for a in range(0, wl.nframes, step):
+        b = min(a + step, wl.nframes)
+        got = wl.buf[wl.frame_off[a:b, None] + col[None, :]]
+        live = col[None, :] < torch.from_numpy(hl[a:b]).to(wl.dev)[:, None]
+        same = (got == torch.from_numpy(rows[a:b]).to(wl.dev)) | ~live
+        if not bool(same.all()):
+            i = int(torch.nonzero(~same.all(dim=1))[0])
+            raise AssertionError("header of frame %d is %s, the generator's is %s"
+                                 % (a + i, got[i].cpu().numpy()[:int(hl[a + i])], rows[a + i][:int(hl[a + i])]))
+
+
 @pytest.mark.parametrize("cfg", ["cfg2", "cfg3", "cfg4", "cfg5"])
 def test_full_size_properties(dev, cfg):
     """BASELINE configs at full size (cfg4: one GPU's share of the 8-GPU batch, 1 M x 64 KiB =
     68.7 GB of wire in 16-frame rx segments): decode -> generator plaintext; decode again ->
-    wire bytes; descriptors/segment results consistent with the generator's lengths"""
+    wire bytes; descriptors/segment results consistent with the generator's lengths; after each
+    decode every frame's header bytes are the generator's (verify reads payloads only)"""
     import bench
     wl = bench.Workload.make(cfg, dev)
     try:
+        rows, hl = generator_headers(wl)
         wl.decode()
         torch.cuda.synchronize()
         assert wl.verify(expect_plain=True) == 0
+        assert_headers(wl, rows, hl)
         res = wl.res.view(torch.int64).view(-1, 2)
         assert int(res[:, 0].sum()) == wl.wire_bytes
         nf = (res[:, 1] & 0xFFFFFFFF)
@@ -229,6 +270,7 @@ def test_full_size_properties(dev, cfg):
         wl.decode()
         torch.cuda.synchronize()
         assert wl.verify(expect_plain=False) == 0
+        assert_headers(wl, rows, hl)
     finally:
         wl.free()
 

@@ -38,18 +38,20 @@ def u32(t):
     return t.cpu().numpy().view(np.uint32)
 
 
-def validate(dev, out, desc, msg, nmsg, mf, state, conns, segs, tag=""):
+def validate(dev, out, desc, msg, nmsg, mf, state, conns, segs, tag="", out_window=None):
     """one validator call on device tensors; segs[s] = the oracle's view of segment s's listed
     messages [(opcode, body, complete, continued, n_frames)]; conns[s] its TextConn. Compares
-    everything the call writes and everything it must not write."""
+    everything the call writes and everything it must not write (of d_out the bytes
+    [out_window[0], out_window[1]) where one is given: an arena is never copied as a whole)."""
     nseg = len(segs)
     verdict = torch.full((nseg * mf,), SENTINEL, dtype=torch.int32, device=dev)
     first_bad = torch.full((nseg,), SENTINEL, dtype=torch.int32, device=dev)
-    before = [t.clone() for t in (out, desc, msg)]
+    seen = out if out_window is None else out[out_window[0]:out_window[1]]
+    before = [t.clone() for t in (seen, desc, msg)]
     st_in = None if state is None else u32(state).copy()
     W.batch_validate_text_device(out, desc, msg, nmsg, mf, verdict, text_state=state, first_bad=first_bad)
     torch.cuda.synchronize()
-    for t, b, name in zip((out, desc, msg), before, ("d_out", "d_desc", "d_msg")):
+    for t, b, name in zip((seen, desc, msg), before, ("d_out", "d_desc", "d_msg")):
         assert torch.equal(t, b), "%s %s modified" % (tag, name)
     gv, gf = u32(verdict).reshape(nseg, mf), u32(first_bad)
     gs = None if state is None else u32(state)
@@ -64,10 +66,13 @@ def validate(dev, out, desc, msg, nmsg, mf, state, conns, segs, tag=""):
     return gv
 
 
-def direct(dev, segs, mf, conns=None, state=None, phases=None, tag=""):
+def direct(dev, segs, mf, conns=None, state=None, phases=None, tag="", arena=None, base=0):
     """hand-built d_out / d_msg / d_desc: message i of a segment takes frame slot i; bodies are
     laid out one after the other, each at its 16-B phase (phases[s][i], default cycling), with
-    0xFF / 0xC2 / 0xF0 in every byte between them, immediately before and after each body"""
+    0xFF / 0xC2 / 0xF0 in every byte between them, immediately before and after each body.
+    With arena (a high_arena.Arena) the layout goes to arena offset `base`, the arena's tensor is
+    d_out and every out_off is base + the layout's: the phases then turn by base % 16; the layout,
+    its guards and its low aliases are compared after the call"""
     nseg = len(segs)
     conns = conns or [T.TextConn(track=state is not None) for _ in range(nseg)]
     msg = np.zeros(nseg * mf, dtype=W.MSG_DTYPE)
@@ -81,18 +86,25 @@ def direct(dev, segs, mf, conns=None, state=None, phases=None, tag=""):
             parts.append(np.resize(np.roll(np.array(POISON, np.uint8), k), gap))
             pos += gap
             parts.append(np.frombuffer(bytes(body), np.uint8))
-            msg[s * mf + i] = (pos, len(body), i, n_frames, complete, continued)
+            msg[s * mf + i] = (base + pos, len(body), i, n_frames, complete, continued)
             desc[s * mf + i]["type"] = 0 if continued else opcode
             desc[s * mf + i]["datalen"] = len(body)
             desc[s * mf + i]["ret"] = 2 + len(body)
             pos += len(body)
             k += 1
     parts.append(np.resize(np.array(POISON, np.uint8), 48))
-    out = torch.from_numpy(np.concatenate(parts)).to(dev)
-    assert out.data_ptr() % 16 == 0
     nmsg = torch.tensor([len(ms) for ms in segs], dtype=torch.int32, device=dev)
     d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
     d_msg = torch.from_numpy(msg.view(np.uint8)).to(dev)
+    if arena is not None:
+        img = np.concatenate(parts)
+        placed = arena.put(base, img)
+        gv = validate(dev, arena.t, d_desc, d_msg, nmsg, mf, state, conns, segs, tag,
+                      out_window=(base - 64, base + len(img) + 64))
+        arena.check(placed, img, tag)
+        return gv
+    out = torch.from_numpy(np.concatenate(parts)).to(dev)
+    assert out.data_ptr() % 16 == 0
     return validate(dev, out, d_desc, d_msg, nmsg, mf, state, conns, segs, tag)
 
 
@@ -110,9 +122,7 @@ def filler(n, seed=0):
 LENGTHS = [0, 1, 2, 3, 15, 16, 17] + [e + d for e in (CHUNK, ROW, TILE) for d in (-1, 0, 1)]
 
 
-def test_lengths_and_phases(dev):
-    """every length around the chunk, row and tile sizes at every 16-B phase: ASCII, mixed
-    sequences, and the same with the last byte cut to a lead"""
+def lengths_and_phases(dev, **where):
     ms, ph = [], []
     for n in sorted(set(LENGTHS)):
         for p in range(16):
@@ -121,13 +131,17 @@ def test_lengths_and_phases(dev):
                 ms.append((1, body, 0, 0, 1) if p % 4 == 0 else (2, body, 1, 0, 1))
                 ph += [p, p]
     half = len(ms) // 2
-    gv = direct(dev, [ms[:half], ms[half:]], half + 3, phases=[ph[:half], ph[half:]], tag="lengths")
+    gv = direct(dev, [ms[:half], ms[half:]], half + 3, phases=[ph[:half], ph[half:]], tag="lengths", **where)
     assert (gv == T.INVALID).any() and (gv == T.VALID).any() and (gv == T.NA).any()
 
 
-def test_sequences_across_every_edge(dev):
-    """a 2-, 3- and 4-byte sequence across every chunk, row and tile edge (every way of cutting
-    it), at every phase; and the same with its byte after the edge broken"""
+def test_lengths_and_phases(dev):
+    """every length around the chunk, row and tile sizes at every 16-B phase: ASCII, mixed
+    sequences, and the same with the last byte cut to a lead"""
+    lengths_and_phases(dev)
+
+
+def sequences_across_every_edge(dev, **where):
     ms, ph = [], []
     for edge in (CHUNK, ROW, TILE, TILE + ROW, 2 * TILE):
         for p in range(16):
@@ -142,8 +156,14 @@ def test_sequences_across_every_edge(dev):
                     body[at + j] = 0x41 if p % 2 else 0xC2
                     ms.append((1, bytes(body), 1, 0, 1))
                     ph += [p, p]
-    gv = direct(dev, [ms], len(ms), phases=[ph], tag="edges")
+    gv = direct(dev, [ms], len(ms), phases=[ph], tag="edges", **where)
     assert (gv[0, 0::2] == T.VALID).all() and (gv[0, 1::2] == T.INVALID).all()
+
+
+def test_sequences_across_every_edge(dev):
+    """a 2-, 3- and 4-byte sequence across every chunk, row and tile edge (every way of cutting
+    it), at every phase; and the same with its byte after the edge broken"""
+    sequences_across_every_edge(dev)
 
 
 def test_single_bad_byte_positions(dev):
@@ -212,25 +232,29 @@ CARRY_SEQS = [bytes.fromhex(h) for h in ("c2a2", "e0a080", "e18080", "ed9fbf", "
                                          "e08080", "eda080", "f08f8080", "f4908080", "e0a041", "f09080c2")]
 
 
-def test_carry_between_batches(dev):
-    """sequences split between batches with 1, 2 and 3 pending bytes (every restricted lead, good
-    and bad second bytes), one byte per batch, an empty continued body; all at two phases"""
+def carry_between_batches(dev, **where):
     cases = [(q, j) for q in CARRY_SEQS for j in range(1, len(q))]
     n = len(cases)
     state = torch.zeros(3 * n, dtype=torch.int32, device=dev)
     conns = [T.TextConn() for _ in range(3 * n)]
     # a: two batches; b: the bytes after the cut one per batch; c: an empty batch in between
     b1 = [[(1, b"ab" + q[:j], 0, 0, 1)] for q, j in cases] * 3
-    direct(dev, b1, 2, conns, state, phases=[[13]] * (3 * n), tag="carry 1")
+    direct(dev, b1, 2, conns, state, phases=[[13]] * (3 * n), tag="carry 1", **where)
     pend = u32(state)[:n] >> 24 & 3
     assert sorted(set(pend)) == [0, 1, 2, 3]               # FAILED ones have n = 0
     b2 = ([[(1, q[j:] + b"z", 1, 1, 1), (1, b"next", 1, 0, 1)] for q, j in cases] +
           [[(1, q[j:j + 1], 0, 1, 1)] for q, j in cases] + [[(1, b"", 0, 1, 1)] for q, j in cases])
-    direct(dev, b2, 2, conns, state, phases=[[15, 0]] * (3 * n), tag="carry 2")
+    direct(dev, b2, 2, conns, state, phases=[[15, 0]] * (3 * n), tag="carry 2", **where)
     b3 = ([[] for _ in cases] + [[(1, q[j + 1:] + b"z", 1, 1, 3)] for q, j in cases] +
           [[(1, q[j:] + b"z", 0, 1, 1)] for q, j in cases])
-    direct(dev, b3, 2, conns, state, phases=[[1]] * (3 * n), tag="carry 3")
+    direct(dev, b3, 2, conns, state, phases=[[1]] * (3 * n), tag="carry 3", **where)
     assert not u32(state)[:2 * n].any() and (u32(state)[2 * n:] & T.ST_PENDING).all()
+
+
+def test_carry_between_batches(dev):
+    """sequences split between batches with 1, 2 and 3 pending bytes (every restricted lead, good
+    and bad second bytes), one byte per batch, an empty continued body; all at two phases"""
+    carry_between_batches(dev)
 
 
 def test_state_rules(dev):
