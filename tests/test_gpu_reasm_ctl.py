@@ -42,16 +42,18 @@ def reasm_path(request):
 class Bufs:
     """device buffers of one call, outputs prefilled with 0xEE"""
 
-    def __init__(self, dev, wire, so, sl, mf, open_in=None, out_off=None, out_size=None, cached_in=None):
+    def __init__(self, dev, wire, so, sl, mf, open_in=None, out_off=None, out_size=None, cached_in=None, shift=0,
+                 out_shift=0):
         n, nseg = len(wire), len(so)
         self.n, self.nseg, self.mf = n, nseg, mf
-        self.d = torch.zeros(n + 64, dtype=torch.uint8, device=dev)
+        self.d = torch.zeros(shift + n + 64, dtype=torch.uint8, device=dev)[shift:]    # base phases: slack + slice
         if n:
             self.d[:n] = torch.from_numpy(wire).to(dev)
         T = lambda a: torch.tensor(np.asarray(a, dtype=np.int64), device=dev)  # noqa: E731
         self.so, self.sl = T(so), T(sl)
         self.out_off = None if out_off is None else T(out_off)
-        self.out = torch.full(((out_size or n) + 64,), FILL, dtype=torch.uint8, device=dev)
+        self.out = torch.full((out_shift + (out_size or n) + 64,), FILL, dtype=torch.uint8, device=dev)[out_shift:]
+        assert (self.d.data_ptr() & 15, self.out.data_ptr() & 15) == (shift & 15, out_shift & 15)
         self.desc = torch.full((max(1, nseg * mf) * 32,), FILL, dtype=torch.uint8, device=dev)
         self.msg = torch.full((max(1, nseg * mf) * 32,), FILL, dtype=torch.uint8, device=dev)
         self.res = torch.zeros(max(1, nseg) * 16, dtype=torch.uint8, device=dev)
@@ -74,8 +76,8 @@ class Bufs:
 
 
 def gpu_ctl(dev, wire, so, sl, mf, open_in=None, out_off=None, out_size=None, readcache_max=0, cached_in=None,
-            flags=CTL):
-    b = Bufs(dev, wire, so, sl, mf, open_in, out_off, out_size, cached_in)
+            flags=CTL, shift=0, out_shift=0):
+    b = Bufs(dev, wire, so, sl, mf, open_in, out_off, out_size, cached_in, shift, out_shift)
     b.call(readcache_max, flags)
     h = b.host()
     assert np.array_equal(b.d[:len(wire)].cpu().numpy(), wire), "wire buffer modified"
@@ -106,9 +108,17 @@ def compare(got, oracle, so, sl, mf, out_off=None, tag=""):
         assert np.array_equal(gca, oca), tag
 
 
-def check(dev, wire, so, sl, mf, open_in=None, out_off=None, out_size=None, readcache_max=0, cached_in=None, tag=""):
-    got = gpu_ctl(dev, wire, so, sl, mf, open_in, out_off, out_size, readcache_max, cached_in)
-    orc = oracle_reassemble_ctl(wire, so, sl, mf, open_in, out_off, readcache_max, cached_in)
+def check(dev, wire, so, sl, mf, open_in=None, out_off=None, out_size=None, readcache_max=0, cached_in=None, tag="",
+          shift=0, out_shift=0, buflen=None, oracle=None):
+    """shift / out_shift: the buffers' base phases; buflen: passed to the entry point as it is;
+    oracle: oracle_reassemble_ctl's output for these arguments, where the caller has it already"""
+    if buflen is None:
+        got = gpu_ctl(dev, wire, so, sl, mf, open_in, out_off, out_size, readcache_max, cached_in, CTL, shift, out_shift)
+    else:
+        from test_gpu_reasm import gpu_reassemble
+        got = gpu_reassemble(dev, wire, so, sl, mf, open_in, out_off, out_size, readcache_max, cached_in, shift,
+                             out_shift, CTL, buflen)
+    orc = oracle or oracle_reassemble_ctl(wire, so, sl, mf, open_in, out_off, readcache_max, cached_in)
     compare(got, orc, so, sl, mf, out_off, tag)
     return orc
 
