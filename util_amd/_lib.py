@@ -52,7 +52,12 @@ _ctl = None
 TEXT_LIB_PATH = os.path.join(HERE, "libwsframe_amd_text.so")
 TEXT_EXPORTS = ["websocketframeBatchValidateTextDevice"]
 _text = None
-_options = {}            # options set through set_option(): the ctl and text libraries keep their own copies
+# libwsframe_amd_proto.so: everything libwsframe_amd_text.so exports plus the WSFRAME_AMD_PROTO_EXPORT
+# entry points (include/wsframe_amd_proto.h)
+PROTO_LIB_PATH = os.path.join(HERE, "libwsframe_amd_proto.so")
+PROTO_EXPORTS = ["websocketframeBatchCheckProtocolDevice", "websocketframeProtoStepHost"]
+_proto = None
+_options = {}            # options set through set_option(): the ctl, text and proto libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -154,6 +159,8 @@ def set_option(name, value):
             _ctl.websocketframeGpuSetOption(name.encode(), int(value))
         if _text is not None:
             _text.websocketframeGpuSetOption(name.encode(), int(value))
+        if _proto is not None:
+            _proto.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -219,6 +226,43 @@ def load_text_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _text = lib
+    return lib
+
+
+def load_proto_lib():
+    """libwsframe_amd_proto.so: websocketframeBatchCheckProtocolDevice and websocketframeProtoStepHost
+    next to the whole C ABI of libwsframe_amd_text.so (decode, reassembly, text validation and the
+    protocol check on one workspace). A library of its own state, as load_text_lib(): the options
+    set so far are applied when it loads and forwarded afterwards."""
+    global _proto
+    if _proto is not None:
+        return _proto
+    load_lib()
+    if not os.path.exists(PROTO_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_proto.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(PROTO_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchCheckProtocolDevice.restype = i32
+    lib.websocketframeBatchCheckProtocolDevice.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp]
+    lib.websocketframeProtoStepHost.restype = i32
+    lib.websocketframeProtoStepHost.argtypes = [C.POINTER(u64), C.c_ubyte, i32, u64, C.c_char_p, u32, u32, u64]
+    lib.websocketframeBatchDecodeDevice.restype = i32
+    lib.websocketframeBatchDecodeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.websocketframeStreamDecodeDevice.restype = i32
+    lib.websocketframeStreamDecodeDevice.argtypes = [vp, u64, u32, vp, vp, vp]
+    lib.websocketframeBatchReassembleDeviceCtl.restype = i32
+    lib.websocketframeBatchReassembleDeviceCtl.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp,
+                                                           u32, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    lib.websocketframeGpuGetStat.restype = i32
+    lib.websocketframeGpuGetStat.argtypes = [C.c_char_p, C.POINTER(C.c_ulonglong)]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _proto = lib
     return lib
 
 

@@ -200,6 +200,8 @@ struct WsStreamWs {
     size_t ews_bytes = 0;
     void* tws = nullptr;           // text validation workspace (ws_utf8.hip: per-slot records + tile scan)
     size_t tws_bytes = 0;
+    void* pws = nullptr;           // protocol check workspace (ws_proto.hip: segment offsets + tile summaries)
+    size_t pws_bytes = 0;
     void* aws = nullptr;           // auxiliary device scratch (the stream path's chunk-parallel walk)
     size_t aws_bytes = 0;
     void* hws = nullptr;           // ... and its pinned host copy
@@ -230,7 +232,7 @@ size_t ws_workspace_bytes_total() {
     size_t t = 0;
     for (auto& d : g_dev) {
         for (auto& w : d.sw) {
-            t += w.ws_bytes + w.ews_bytes + w.aws_bytes + w.tws_bytes;
+            t += w.ws_bytes + w.ews_bytes + w.aws_bytes + w.tws_bytes + w.pws_bytes;
             for (auto& r : w.retired) t += r.second;
         }
         for (auto& r : d.deferred) t += r.second;
@@ -275,14 +277,15 @@ static void slot_free(WsStreamWs& w) {
     (void)hipFree(w.ws);
     (void)hipFree(w.ews);
     (void)hipFree(w.tws);
+    (void)hipFree(w.pws);
     (void)hipFree(w.aws);
     if (w.hws) (void)hipHostFree(w.hws);
     if (w.adv_h) (void)hipHostFree(w.adv_h);
     for (auto& r : w.retired) (void)hipFree(r.first);
     w.retired.clear();
-    w.ws = nullptr; w.ews = nullptr; w.tws = nullptr; w.aws = nullptr; w.hws = nullptr; w.hws_dev = nullptr;
+    w.ws = nullptr; w.ews = nullptr; w.tws = nullptr; w.pws = nullptr; w.aws = nullptr; w.hws = nullptr; w.hws_dev = nullptr;
     w.adv_h = nullptr; w.adv_d = nullptr;
-    w.ws_bytes = w.ews_bytes = w.tws_bytes = w.aws_bytes = w.hws_bytes = 0;
+    w.ws_bytes = w.ews_bytes = w.tws_bytes = w.pws_bytes = w.aws_bytes = w.hws_bytes = 0;
     w.aux_state_ok = false;
     w.stream = nullptr;
     w.capture = 0;
@@ -522,6 +525,14 @@ int WsSlot::text_workspace(size_t bytes, void** out) {
     const int rc = grow(w, &w->tws, &w->tws_bytes, bytes, st, 0, "hipMalloc(text workspace)");
     if (rc) return rc;
     *out = w->tws;
+    return 0;
+}
+
+int WsSlot::proto_workspace(size_t bytes, void** out) {
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    const int rc = grow(w, &w->pws, &w->pws_bytes, bytes, st, 0, "hipMalloc(protocol check workspace)");
+    if (rc) return rc;
+    *out = w->pws;
     return 0;
 }
 

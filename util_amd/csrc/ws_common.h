@@ -331,6 +331,7 @@ struct WsSlot {
     int workspace(size_t bytes, size_t zero_bytes, void** out);   // decode / reassembly / stream
     int encode_workspace(size_t bytes, void** out);
     int text_workspace(size_t bytes, void** out);                  // the text validator (ws_utf8.hip)
+    int proto_workspace(size_t bytes, void** out);                 // the protocol check (ws_proto.hip)
     int aux(size_t dbytes, size_t hbytes, WsAux* out);
     int advice(int** host, int** dev);                             // the stride hint words (eager)
     int side(hipStream_t* side, hipEvent_t* ev, int prio);         // the raw stream's split walk: side stream + events

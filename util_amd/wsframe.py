@@ -31,6 +31,14 @@ TEXT_NONE = 0xFFFFFFFF
 TEXT_ST_PENDING, TEXT_ST_FAILED = 0x80000000, 0x40000000
 # the validator's geometry (ws_utf8.hip): 16-B chunk per lane, 64 chunks per wave row, 4 rows per tile
 TEXT_CHUNK, TEXT_ROW, TEXT_TILE = 16, 1024, 4096
+# include/wsframe_amd_proto.h: frame codes of batch_check_protocol_device, its flags and state bits
+(PROTO_OK, PROTO_ERR_RSV, PROTO_ERR_OPCODE, PROTO_ERR_MASK, PROTO_ERR_CTL_FRAGMENTED, PROTO_ERR_CTL_LENGTH,
+ PROTO_ERR_CLOSE_LENGTH, PROTO_ERR_CLOSE_CODE, PROTO_ERR_CONT_UNEXPECTED, PROTO_ERR_DATA_INTERLEAVED,
+ PROTO_ERR_TOO_BIG) = range(11)
+PROTO_AFTER_CLOSE, PROTO_NOT_CONSUMED = 0x80, 0x81
+PROTO_EXPECT_MASKED, PROTO_EXPECT_UNMASKED, PROTO_WIRE_MASKED = 1, 2, 4
+PROTO_NONE = 0xFFFFFFFF
+PROTO_ST_OPEN, PROTO_ST_CLOSED, PROTO_BYTES_MAX = 1 << 63, 1 << 62, (1 << 56) - 1
 NETPACKET_FRAGMENT = 6  # transport_ctx.h:11-18; the pktype websocketframeOnDecode reports
 DATA_OFF_NULL = 0xFFFFFFFFFFFFFFFF
 BATCH_PAD = 32  # WEBSOCKET_BATCH_PAD: readable device bytes required after every segment
@@ -44,6 +52,8 @@ assert MSG_DTYPE.itemsize == 32
 ENC_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u8"), ("mask_key", "<u4"), ("type", "u1"), ("is_fin", "u1"),
                       ("prev_is_fin", "u1"), ("masked", "u1")])
 assert ENC_DTYPE.itemsize == 24
+PROTO_RES_DTYPE = np.dtype([("first_bad", "<u4"), ("code", "<u4"), ("close_status", "<u4"), ("close_frame", "<u4")])
+assert PROTO_RES_DTYPE.itemsize == 16
 assert DESC_DTYPE.itemsize == C.sizeof(WsDesc) == 32
 assert SEGRES_DTYPE.itemsize == C.sizeof(WsSegRes) == 16
 
@@ -214,6 +224,36 @@ def batch_validate_text_device(out, desc, msg, nmsg, max_frames, verdict, text_s
     rc = lib.websocketframeBatchValidateTextDevice(_ptr(out), _ptr(desc), _ptr(msg), _ptr(nmsg), nseg, max_frames,
                                                    _ptr(text_state), _ptr(verdict), _ptr(first_bad), _stream(stream))
     check(rc, "websocketframeBatchValidateTextDevice", lib)
+
+
+def batch_check_protocol_device(buf, seg_off, desc, res, max_frames, proto_res, flags=0, rsv_allowed=0,
+                                max_message_size=0, proto_state=None, frame_code=None, stream=None):
+    """websocketframeBatchCheckProtocolDevice (libwsframe_amd_proto.so) on what a decode or reassembly
+    call on the same stream just produced: buf (uint8, the wire), seg_off (int64 nseg), desc (uint8
+    >= 32*nseg*max_frames), res (uint8 16*nseg); proto_res (uint8 16*nseg: PROTO_RES_DTYPE records),
+    proto_state (int64 nseg, in/out, optional: the per-connection carry, zero when the connection
+    starts), frame_code (uint8 >= nseg*max_frames, optional: the code of frame k of segment s at
+    s*max_frames + k, k < n_frames; other slots are not written). flags: PROTO_EXPECT_MASKED or
+    PROTO_EXPECT_UNMASKED, and PROTO_WIRE_MASKED after a reassembly call; async on `stream`."""
+    nseg = seg_off.numel()
+    assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
+    assert res.numel() * res.element_size() >= 16 * nseg
+    assert proto_res.numel() * proto_res.element_size() >= 16 * nseg
+    assert proto_state is None or proto_state.numel() * proto_state.element_size() >= 8 * nseg
+    assert frame_code is None or frame_code.numel() * frame_code.element_size() >= nseg * max_frames
+    lib = _lib.load_proto_lib()
+    rc = lib.websocketframeBatchCheckProtocolDevice(_ptr(buf), _ptr(seg_off), _ptr(desc), _ptr(res), nseg, max_frames,
+                                                    int(flags), int(rsv_allowed), int(max_message_size),
+                                                    _ptr(proto_state), _ptr(frame_code), _ptr(proto_res), _stream(stream))
+    check(rc, "websocketframeBatchCheckProtocolDevice", lib)
+
+
+def proto_step_host(state, b0, masked, datalen, body2=None, flags=0, rsv_allowed=0, max_message_size=0):
+    """websocketframeProtoStepHost: (code, new state) of one consumed frame on the host path"""
+    st = C.c_ulonglong(state)
+    code = _lib.load_proto_lib().websocketframeProtoStepHost(C.byref(st), b0, int(masked), datalen, body2, flags,
+                                                             rsv_allowed, max_message_size)
+    return code, st.value
 
 
 def batch_encode_device(src, frames, dst, wire_off, capacity=None, stream=None):
