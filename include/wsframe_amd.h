@@ -195,8 +195,10 @@ WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHost(unsigned char* h_buf, unsig
  * websocketframeBatchDecodeHost's pipeline on devices[i] from its own host thread; results land
  * in h_desc / h_res exactly where the one-device call puts them. A device may be listed more than
  * once (its ranges then run one after the other). Any other segment layout (unordered,
- * overlapping) or ndev == 1 is the one-device call on devices[0]. Synchronous; returns 0 or the
- * first failing range's error (websocketframeGpuLastError names its device). */
+ * overlapping) or ndev == 1 is the one-device call on devices[0]. A device index outside [0, 64)
+ * or a segment outside h_buf fails the call before any range runs (nothing is written).
+ * Synchronous; returns 0 or the first failing range's error (websocketframeGpuLastError names its
+ * device). */
 WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHostMulti(unsigned char* h_buf, unsigned long long buflen,
                                                           const unsigned long long* h_seg_off,
                                                           const unsigned long long* h_seg_len, unsigned int nseg,
@@ -269,7 +271,8 @@ WSFRAME_AMD_EXPORT int websocketframeGpuSetOption(const char* name, long long va
  * lengths that keep changing), "stream_splits" (raw-stream calls since load whose unmask
  * ran as two launches beside the split walk, option "stream_split"), "capture_adoptions" (graph captures since load that took over the
  * workspace slot of a destroyed graph whose replays had all finished), "capture_adoption_refusals" (captures
- * since load that passed over such a slot because a replay of its graph was still queued), "k2_windows" (the
+ * since load that passed over such a slot because a replay of its graph was still queued), "host_groups" (the groups
+ * websocketframeBatchDecodeHost(Multi) calls launched since load: one H2D copy, one decode and one write-back each), "k2_windows" (the
  * piece windows of the most recent unmask launch: 1 << the "piece_win" rule's choice); with the option
  * "k2_timing" set, "k2_ns" / "k2_calls" (the summed duration and count of the piece
  * path's unmask launches since the option was set, from HIP events around each launch;

@@ -39,6 +39,7 @@ extern WsOpt ws_stream_win, ws_stream_split_capture, ws_stream_split, ws_stream_
 size_t ws_workspace_bytes_total();
 extern std::atomic<unsigned long long> ws_stat_rw_chunks, ws_stat_rw_chunk_walks, ws_stat_stream_skips,
     ws_stat_stream_splits;
+extern std::atomic<unsigned long long> ws_stat_host_groups;
 extern std::atomic<unsigned long long> ws_stat_adoptions;
 extern std::atomic<unsigned long long> ws_stat_k2_windows;
 extern std::atomic<unsigned long long> ws_stat_adoption_refusals;
@@ -171,6 +172,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, uns
     else if (!strcmp(name, "capture_adoptions")) *value = ws_stat_adoptions.load();
     else if (!strcmp(name, "k2_windows")) *value = ws_stat_k2_windows.load();
     else if (!strcmp(name, "capture_adoption_refusals")) *value = ws_stat_adoption_refusals.load();
+    else if (!strcmp(name, "host_groups")) *value = ws_stat_host_groups.load();
 
     else return -1;
     return 0;

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "ws_common.h"
+#include "ws_hostplan.h"
 
 #define WS_HOST_DEV 64
 #define WS_HOST_SLOTS 3
@@ -58,10 +59,9 @@ static int grow(T** p, size_t* cap, size_t need, const char* what) {
     return 0;
 }
 
-struct Group {
-    u32 s0, s1;   // segments [s0, s1)
-    u64 lo, hi;   // host byte span [lo, hi)
-};
+std::atomic<unsigned long long> ws_stat_host_groups{0};   // groups launched by host decodes (since load)
+
+static_assert(sizeof(WebsocketFrameDesc_t) == WS_HOSTPLAN_DESC_BYTES, "ws_hostplan.h counts descriptors of this size");
 
 struct DeviceGuard {          // restores the calling thread's current device on every return
     int dev = -1;
@@ -77,63 +77,26 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHost(unsigned char* h
     if (nseg == 0) return 0;
     if (!h_buf || !h_seg_off || !h_seg_len || !h_desc || !h_res || max_frames == 0)
         return ws_set_msg("websocketframeBatchDecodeHost: invalid argument");
-    if (device < 0 || device >= WS_HOST_DEV) return ws_set_err("device index", hipErrorInvalidDevice);
+    if (device < 0 || device >= WS_HOST_DEV)
+        return ws_set_err("websocketframeBatchDecodeHost: device index", hipErrorInvalidDevice);
     DeviceGuard guard;
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return ws_set_err("hipSetDevice", e);
 
-    // groups of consecutive, ascending, non-overlapping segments of about one chunk;
-    // any other layout is decoded as one group spanning all segments
-    bool ordered = true;
-    u64 prev_end = 0, lo_all = ~0ull, hi_all = 0;
-    for (u32 s = 0; s < nseg; ++s) {
-        const u64 o = h_seg_off[s], l = h_seg_len[s];
-        if (o > buflen || l > buflen - o) return ws_set_msg("websocketframeBatchDecodeHost: segment outside buffer");
-        if (o < prev_end) ordered = false;
-        prev_end = o + l;
-        lo_all = o < lo_all ? o : lo_all;
-        hi_all = o + l > hi_all ? o + l : hi_all;
-    }
-    const size_t desc_cap_bytes = 64ull << 20;
-    std::vector<Group> groups;
-    if (!ordered) {
-        groups.push_back(Group{0, nseg, lo_all, hi_all});
-    } else {
-        for (u32 s = 0; s < nseg;) {
-            Group g{s, s + 1, h_seg_off[s], h_seg_off[s] + h_seg_len[s]};
-            while (g.s1 < nseg) {
-                const u64 end = h_seg_off[g.s1] + h_seg_len[g.s1];
-                if (end - g.lo > ws_host_chunk_bytes) break;
-                if ((size_t)(g.s1 + 1 - g.s0) * max_frames * sizeof(WebsocketFrameDesc_t) > desc_cap_bytes) break;
-                g.hi = end;
-                ++g.s1;
-            }
-            groups.push_back(g);
-            s = g.s1;
-        }
-    }
-    // the host ranges written back per group: its segments' bytes, in buffer order, adjacent
-    // segments merged
-    std::vector<std::vector<std::pair<u64, u64>>> back(groups.size());
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& g = groups[gi];
-        std::vector<std::pair<u64, u64>> r;
-        r.reserve(g.s1 - g.s0);
-        for (u32 s = g.s0; s < g.s1; ++s)
-            if (h_seg_len[s]) r.emplace_back(h_seg_off[s], h_seg_off[s] + h_seg_len[s]);
-        if (!ordered) std::sort(r.begin(), r.end());
-        for (const auto& x : r) {
-            if (!back[gi].empty() && x.first <= back[gi].back().second)
-                back[gi].back().second = std::max(back[gi].back().second, x.second);
-            else
-                back[gi].push_back(x);
-        }
-    }
-    size_t max_span = 0, max_nseg = 0;
-    for (const Group& g : groups) {
-        max_span = g.hi - g.lo > max_span ? g.hi - g.lo : max_span;
-        max_nseg = g.s1 - g.s0 > max_nseg ? g.s1 - g.s0 : max_nseg;
-    }
+    // groups of consecutive, ascending, non-overlapping segments of about one chunk, any other
+    // layout one group; the host ranges written back per group (ws_hostplan.h)
+    const WsHostPlan plan = ws_host_plan(h_seg_off, h_seg_len, nseg, max_frames, buflen, ws_host_chunk_bytes);
+    if (plan.outside) return ws_set_msg("websocketframeBatchDecodeHost: segment outside buffer");
+    const std::vector<WsHostGroup>& groups = plan.groups;
+    std::vector<std::vector<std::pair<uint64_t, uint64_t>>> back(groups.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        ws_host_back_ranges(h_seg_off, h_seg_len, groups[gi], plan.ordered, back[gi]);
+    const size_t max_span = plan.max_span, max_nseg = plan.max_nseg;
+    // the decode picks its path per group (ws_decode_range): the slots' workspace is the largest any
+    // group asks for, so no group outgrows its slot's workspace or falls through to the stream's
+    size_t wsb = 0;
+    for (const WsHostGroup& g : groups)
+        wsb = std::max(wsb, ws_decode_workspace_bytes(g.hi - g.lo, g.s1 - g.s0, max_frames));
 
     WsHostPipe& P = g_pipe[device];
     std::lock_guard<std::mutex> lock(P.mu);
@@ -148,7 +111,6 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHost(unsigned char* h
         if ((rc = grow(&S.segs, &S.seg_cap, 2 * max_nseg, "hipMalloc(host slot segs)"))) return rc;
         if ((rc = grow(&S.desc, &S.desc_cap, max_nseg * max_frames, "hipMalloc(host slot desc)"))) return rc;
         if ((rc = grow(&S.res, &S.res_cap, max_nseg, "hipMalloc(host slot res)"))) return rc;
-        const size_t wsb = ws_decode_workspace_bytes(max_span, (u32)max_nseg, max_frames);
         if (wsb && S.ws_cap < wsb) {
             if ((rc = grow(&S.ws, &S.ws_cap, wsb, "hipMalloc(host slot workspace)"))) return rc;
             if ((e = hipMemset(S.ws, 0, 16)) != hipSuccess) return ws_set_err("hipMemset(host slot workspace)", e);
@@ -156,7 +118,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHost(unsigned char* h
     }
 #define WS_TRY(call, what) do { if ((e = (call)) != hipSuccess) { rc = ws_set_err(what, e); goto drain; } } while (0)
     for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& g = groups[gi];
+        const WsHostGroup& g = groups[gi];
         WsHostSlot& S = P.slot[gi % nslots];
         const u32 n = g.s1 - g.s0;
         const size_t span = g.hi - g.lo;
@@ -170,6 +132,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHost(unsigned char* h
         rc = ws_decode_range(S.buf - g.lo, g.lo, g.hi, S.segs, S.segs + S.seg_cap / 2, n, max_frames, nullptr, S.desc,
                              S.res, S.st, S.ws, S.ws_cap);
         if (rc) goto drain;
+        ++ws_stat_host_groups;
         for (const auto& x : back[gi])
             WS_TRY(hipMemcpyAsync(h_buf + x.first, S.buf + (x.first - g.lo), x.second - x.first, hipMemcpyDeviceToHost,
                                   S.st), "D2H batch");
@@ -194,7 +157,8 @@ drain:
 // pipeline on its own device from its own host thread, so every device's PCIe link carries its
 // share (one pinned arena served by up to ndev links). A device listed twice runs its ranges one
 // after the other (its pipeline is locked per device). Any other segment layout is decoded on
-// devices[0] alone. Returns the first range's error (every range is drained first).
+// devices[0] alone. A device index or a segment out of range fails the call before any range
+// runs; otherwise it returns the first range's error (every range is drained first).
 extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHostMulti(unsigned char* h_buf, unsigned long long buflen,
                                                                      const u64* h_seg_off, const u64* h_seg_len,
                                                                      unsigned int nseg, unsigned int max_frames,
@@ -204,31 +168,24 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchDecodeHostMulti(unsigned ch
     if (nseg == 0) return 0;
     if (!devices || ndev <= 0 || !h_seg_off || !h_seg_len)
         return ws_set_msg("websocketframeBatchDecodeHostMulti: invalid argument");
-    bool ordered = true;
-    u64 prev_end = 0, total = 0;
-    for (u32 s = 0; s < nseg; ++s) {
-        if (h_seg_off[s] < prev_end) ordered = false;
-        prev_end = h_seg_off[s] + h_seg_len[s];
-        total += h_seg_len[s];
-    }
-    if (!ordered || ndev == 1 || nseg < 2)
+    // what no range may find out after another has written its results: a device index or a segment
+    // out of range fails the whole call before anything runs
+    for (int r = 0; r < ndev; ++r)
+        if (devices[r] < 0 || devices[r] >= WS_HOST_DEV) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "websocketframeBatchDecodeHostMulti (device %d): device index: %s", devices[r],
+                     hipGetErrorString(hipErrorInvalidDevice));
+            ws_set_msg(msg);
+            return -(int)hipErrorInvalidDevice;
+        }
+    if (!ws_host_inside(h_seg_off, h_seg_len, nseg, buflen))
+        return ws_set_msg("websocketframeBatchDecodeHostMulti: segment outside buffer");
+    if (ws_host_multi_single(ws_host_ordered(h_seg_off, h_seg_len, nseg), nseg, ndev))
         return websocketframeBatchDecodeHost(h_buf, buflen, h_seg_off, h_seg_len, nseg, max_frames, h_desc, h_res,
                                              devices[0]);
-    // cuts: the segment boundary nearest to each equal share of the bytes
-    const u32 nd = (u32)std::min<u64>((u64)ndev, nseg);
-    std::vector<u32> cut(nd + 1, 0);
-    cut[nd] = nseg;
-    {
-        u64 acc = 0;
-        u32 s = 0;
-        for (u32 r = 1; r < nd; ++r) {
-            const long double t = (long double)total * r / nd;
-            while (s < nseg && (long double)(acc + h_seg_len[s]) <= t) acc += h_seg_len[s++];
-            // acc <= t < acc + len[s]: the nearer boundary
-            if (s < nseg && (long double)(acc + h_seg_len[s]) - t < t - (long double)acc) acc += h_seg_len[s++];
-            cut[r] = std::max(s, cut[r - 1]);
-        }
-    }
+    // cuts: the segment boundary nearest to each equal share of the bytes (ws_hostplan.h)
+    const std::vector<u32> cut = ws_host_cuts(h_seg_len, nseg, ndev);
+    const u32 nd = (u32)cut.size() - 1;
     std::vector<int> rc(nd, 0);
     std::vector<std::string> err(nd);
     auto part = [&](u32 r) {
