@@ -57,7 +57,12 @@ _text = None
 PROTO_LIB_PATH = os.path.join(HERE, "libwsframe_amd_proto.so")
 PROTO_EXPORTS = ["websocketframeBatchCheckProtocolDevice", "websocketframeProtoStepHost"]
 _proto = None
-_options = {}            # options set through set_option(): the ctl, text and proto libraries keep their own copies
+# libwsframe_amd_hs.so: everything libwsframe_amd_proto.so exports plus the WSFRAME_AMD_HS_EXPORT
+# entry points (include/wsframe_amd_handshake.h)
+HS_LIB_PATH = os.path.join(HERE, "libwsframe_amd_hs.so")
+HS_EXPORTS = ["websocketframeBatchHandshakeDevice", "websocketframeHandshakeHost"]
+_hs = None
+_options = {}            # options set through set_option(): the ctl, text, proto and hs libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -161,6 +166,8 @@ def set_option(name, value):
             _text.websocketframeGpuSetOption(name.encode(), int(value))
         if _proto is not None:
             _proto.websocketframeGpuSetOption(name.encode(), int(value))
+        if _hs is not None:
+            _hs.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -263,6 +270,36 @@ def load_proto_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _proto = lib
+    return lib
+
+
+def load_hs_lib():
+    """libwsframe_amd_hs.so: websocketframeBatchHandshakeDevice and websocketframeHandshakeHost next to
+    the whole C ABI of libwsframe_amd_proto.so (a connection from its upgrade request to its close
+    on one library). A library of its own state, as load_proto_lib(): the options set so far are
+    applied when it loads and forwarded afterwards."""
+    global _hs
+    if _hs is not None:
+        return _hs
+    load_lib()
+    if not os.path.exists(HS_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_hs.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(HS_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchHandshakeDevice.restype = i32
+    lib.websocketframeBatchHandshakeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp]
+    lib.websocketframeHandshakeHost.restype = i32
+    lib.websocketframeHandshakeHost.argtypes = [vp, u32, u32, vp, vp, vp, u32]
+    lib.websocketframeBatchDecodeDevice.restype = i32
+    lib.websocketframeBatchDecodeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _hs = lib
     return lib
 
 

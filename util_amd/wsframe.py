@@ -54,6 +54,13 @@ ENC_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u8"), ("mask_key", "<u4"), (
 assert ENC_DTYPE.itemsize == 24
 PROTO_RES_DTYPE = np.dtype([("first_bad", "<u4"), ("code", "<u4"), ("close_status", "<u4"), ("close_frame", "<u4")])
 assert PROTO_RES_DTYPE.itemsize == 16
+# include/wsframe_amd_handshake.h: the descriptor of batch_handshake_device / handshake_host, its flags, the call flag
+HS_DTYPE = np.dtype([("ret", "<i4"), ("key_off", "<u4"), ("key_len", "<u4"), ("proto_off", "<u4"), ("proto_len", "<u4"),
+                     ("resp_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert HS_DTYPE.itemsize == 32
+HS_NONE = 0xFFFFFFFF
+HS_RESP_WRITTEN, HS_RESP_NO_SPACE, HS_ERR_SEG_LEN = 1, 2, 4
+HS_ECHO_PROTOCOL = 1
 assert DESC_DTYPE.itemsize == C.sizeof(WsDesc) == 32
 assert SEGRES_DTYPE.itemsize == C.sizeof(WsSegRes) == 16
 
@@ -254,6 +261,48 @@ def proto_step_host(state, b0, masked, datalen, body2=None, flags=0, rsv_allowed
     code = _lib.load_proto_lib().websocketframeProtoStepHost(C.byref(st), b0, int(masked), datalen, body2, flags,
                                                              rsv_allowed, max_message_size)
     return code, st.value
+
+
+def batch_handshake_device(buf, seg_off, seg_len, hs, flags=0, accept=None, resp=None, resp_off=None, resp_cap=0,
+                           stream=None, buflen=None):
+    """websocketframeBatchHandshakeDevice (libwsframe_amd_hs.so) on torch CUDA tensors: buf (uint8, only
+    read; the last BATCH_PAD bytes are slack), seg_off/seg_len (int64 nseg), hs (uint8 32*nseg:
+    HS_DTYPE records), accept (uint8 32*nseg, optional), resp (uint8, optional) with slots at
+    resp_off (int64 nseg) or s*resp_cap. flags: 0 or HS_ECHO_PROTOCOL; async on `stream`. buflen
+    defaults to buf.numel() - BATCH_PAD."""
+    nseg = seg_off.numel()
+    assert seg_len.numel() == nseg and hs.numel() * hs.element_size() >= 32 * nseg
+    assert accept is None or accept.numel() * accept.element_size() >= 32 * nseg
+    assert resp is None or resp_off is not None or resp.numel() >= nseg * resp_cap
+    assert resp_off is None or resp_off.numel() >= nseg
+    if buflen is None:
+        assert buf.numel() >= BATCH_PAD, "device batch needs WEBSOCKET_BATCH_PAD bytes of slack"
+        buflen = buf.numel() - BATCH_PAD
+    lib = _lib.load_hs_lib()
+    rc = lib.websocketframeBatchHandshakeDevice(_ptr(buf), int(buflen), _ptr(seg_off), _ptr(seg_len), nseg, int(flags),
+                                                _ptr(hs), _ptr(accept), _ptr(resp), _ptr(resp_off), int(resp_cap),
+                                                _stream(stream))
+    check(rc, "websocketframeBatchHandshakeDevice", lib)
+
+
+def handshake_host(data, flags=0, resp_cap=512, want_accept=True, want_resp=True):
+    """websocketframeHandshakeHost on one request (bytes): returns (HS_DTYPE record, accept bytes
+    (28) or None, response bytes or None). The request is copied into a buffer with BATCH_PAD
+    bytes after it."""
+    lib = _lib.load_hs_lib()
+    buf = np.zeros(len(data) + BATCH_PAD, np.uint8)
+    buf[:len(data)] = np.frombuffer(bytes(data), np.uint8)
+    hs = np.zeros(1, HS_DTYPE)
+    acc = np.zeros(32, np.uint8)
+    resp = np.zeros(max(1, resp_cap), np.uint8)
+    rc = lib.websocketframeHandshakeHost(buf.ctypes.data, len(data), int(flags), hs.ctypes.data,
+                                         acc.ctypes.data if want_accept else None,
+                                         resp.ctypes.data if want_resp else None, int(resp_cap))
+    check(rc, "websocketframeHandshakeHost", lib)
+    d = hs[0]
+    ok = int(d["ret"]) > 0
+    return (d, bytes(acc[:28]) if ok and want_accept else None,
+            bytes(resp[:int(d["resp_len"])]) if int(d["flags"]) & HS_RESP_WRITTEN else None)
 
 
 def batch_encode_device(src, frames, dst, wire_off, capacity=None, stream=None):
