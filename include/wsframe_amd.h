@@ -276,7 +276,21 @@ WSFRAME_AMD_EXPORT int websocketframeGpuSetOption(const char* name, long long va
  * piece windows of the most recent unmask launch: 1 << the "piece_win" rule's choice); with the option
  * "k2_timing" set, "k2_ns" / "k2_calls" (the summed duration and count of the piece
  * path's unmask launches since the option was set, from HIP events around each launch;
- * reading them waits for those launches). Returns 0, or -1 for an unknown name. */
+ * reading them waits for those launches). Returns 0, or -1 for an unknown name.
+ *
+ * "stream_plan_*": the chunk walk's geometry as this process's last chunk-planned raw-stream call chose
+ * it. "stream_plan_path" (1 planned on the device, 2 linked by the host, option "stream_rw" 2),
+ * "stream_plan_nparts", "stream_plan_nchunks", "stream_plan_active" (0: the walk ended in the sample
+ * or the rest was too short for chunks; the parts then hold an earlier call's values), "stream_plan_nf"
+ * (frames before the first part); and for part k = 0..2, with the digit appended, "stream_plan_P0" (the
+ * part's first byte), "..._C0" (chunk bytes), "..._H0" (window bytes), "..._n0" (chunks), "..._capc0"
+ * (candidates per chunk), "..._stgn0" (staged offsets per owner walk), "..._nrows0" (emit rows),
+ * "..._linked0", "..._in_ent0" / "..._in_nf0" / "..._in_state0" (the hand-off into the part: the
+ * chain's entry, the frames before it, 1 continues / 2 the walk ended before it), "..._lk_serial0" (1:
+ * the serial linker linked the part, 0 with linked 1: the parallel one) and "..._lk_walks0" (chunks
+ * the linker walked itself for want of a record). For a device-planned call the getter synchronizes
+ * the device and reads the plan out of that call's workspace; -1 when there was no such call yet or
+ * that workspace is gone. */
 WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, unsigned long long* value);
 
 /* ---- Part 2b: fused decode + fragmented-message reassembly -- */

@@ -233,3 +233,62 @@ extern "C" int ws_link_host_stream(const unsigned char* buf, u64 buf_bytes, u64 
     res->status = fin.status;
     return steps;
 }
+
+// The fill of the walk's per-chunk pools on a chunk grid of the caller's: chunks of C bytes from P (the
+// last one to len), windows of H bytes, the buffer's first byte at an address of phase `lead` (mod 16:
+// R1 scans whole 16-B lines, one wavefront per 4 KiB from the line of the chunk's first byte).
+// counts[4 c ..] for chunk c:
+//   [0] the most plausible positions any one wavefront span of its window holds (RW_WCAP stages 256)
+//   [1] candidates that survive R1's two headers (the chunk's list holds capc)
+//   [2] window walks that leave the window and pass R2's extra headers (RW_S0 record slots)
+//   [3] distinct window exits among them (RW_D owner walks)
+// Returns the number of chunks, -1 on a bad grid.
+extern "C" long long ws_link_host_pool_counts(const unsigned char* buf, u64 buf_bytes, u64 len, u64 P, u64 C, u32 H,
+                                              u32 lead, u32 need_mask, u32* counts, u64 counts_cap) {
+    Model m = {buf, buf_bytes, len, P, C, H, 64, 1, need_mask != 0, nullptr, false};
+    if (P >= len || !C || !H || H > C || (H & 4095) || lead > 15) return -1;
+    const u64 nchunks = (len - P + C - 1) / C;
+    if (nchunks > counts_cap) return -1;
+    for (u64 c = 0; c < nchunks; ++c) {
+        const u64 cs0 = P + c * C, cend = cs0 + C, wend = cs0 + H;
+        // the window's positions as R1 takes them: H bytes from the 16-B line (by address) of the chunk's first byte
+        const u64 a0 = ((lead + cs0) & ~15ull);                              // address - (origin - lead)
+        u32 wave_max = 0, survivors = 0, n0 = 0;
+        std::vector<u64> exits;
+        for (u64 w0 = 0; w0 < H; w0 += 4096) {
+            u32 in_wave = 0;
+            for (u64 q = 0; q < 4096; ++q) {
+                const u64 addr = a0 + w0 + q;
+                if (addr < lead + cs0 || addr >= lead + len) continue;       // positions inside [cs0, len) only
+                const u64 start = addr - lead;
+                u64 h0, h1;
+                load16(m, start, h0, h1);
+                if (!rw_plausible((u32)h0 & 0xFFu, (u32)(h0 >> 8) & 0xFFu, (u32)(h0 >> 16) & 0xFFFFu, m.need_mask)) continue;
+                ++in_wave;
+                u64 pos = start;
+                if (spec_step(m, pos) == 0 && pos < cend && spec_step(m, pos) == 2) continue;
+                ++survivors;
+                pos = start;
+                u32 r = 0;
+                while (pos < wend && (r = spec_step(m, pos)) == 0) {
+                }
+                if (r != 0) continue;                                        // a wrong start, or the stream's walk ends
+                u64 vp = pos;
+                u32 vr = 0;
+                for (u32 v = 0; v < 3 && vp < cend && (vr = spec_step(m, vp)) == 0; ++v) {
+                }
+                if (vr == 2) continue;
+                ++n0;
+                bool seen = false;
+                for (u64 e : exits) seen = seen || e == pos;
+                if (!seen) exits.push_back(pos);
+            }
+            if (in_wave > wave_max) wave_max = in_wave;
+        }
+        counts[4 * c] = wave_max;
+        counts[4 * c + 1] = survivors;
+        counts[4 * c + 2] = n0;
+        counts[4 * c + 3] = (u32)exits.size();
+    }
+    return (long long)nchunks;
+}

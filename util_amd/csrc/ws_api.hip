@@ -164,6 +164,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, uns
         *value = name[3] == 'n' ? ns : calls;
         return 0;
     }
+    if (!strncmp(name, "stream_plan_", 12)) return ws_stream_plan_stat(name + 12, value);
     if (!strcmp(name, "stream_rw_chunks")) *value = ws_stat_rw_chunks.load();
     else if (!strcmp(name, "stream_rw_chunk_walks")) *value = ws_stat_rw_chunk_walks.load();
     else if (!strcmp(name, "stream_skips")) *value = ws_stat_stream_skips.load();
@@ -206,6 +207,7 @@ struct WsStreamWs {
     size_t pws_bytes = 0;
     void* aws = nullptr;           // auxiliary device scratch (the stream path's chunk-parallel walk)
     size_t aws_bytes = 0;
+    unsigned long long aws_gen = 0; // which allocation (or adoption) of the aux scratch this is: never reused
     void* hws = nullptr;           // ... and its pinned host copy
     void* hws_dev = nullptr;       // (its device address)
     size_t hws_bytes = 0;
@@ -229,6 +231,7 @@ struct WsDevState {
 };
 static WsDevState g_dev[WS_MAX_DEV];
 static std::mutex g_dev_mu;        // device init and the stream-slot table
+static unsigned long long g_aux_gen = 0;   // (under g_dev_mu)
 size_t ws_workspace_bytes_total() {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     size_t t = 0;
@@ -289,6 +292,7 @@ static void slot_free(WsStreamWs& w) {
     w.adv_h = nullptr; w.adv_d = nullptr;
     w.ws_bytes = w.ews_bytes = w.tws_bytes = w.pws_bytes = w.aws_bytes = w.hws_bytes = 0;
     w.aux_state_ok = false;
+    w.aws_gen = 0;
     w.stream = nullptr;
     w.capture = 0;
     w.used = false;
@@ -392,6 +396,7 @@ static int stream_slot(WsDevState* ds, hipStream_t stream, WsStreamWs** out) {
         if (rc) return rc;
         w = adopt;
         w->dead = 0;
+        if (w->aws) w->aws_gen = ++g_aux_gen;                      // (its plan was zeroed: another call's now)
         ++ws_stat_adoptions;
         // the buffers its dead graph's capture replaced: free at the next eager call (not inside a capture)
         ds->deferred.insert(ds->deferred.end(), w->retired.begin(), w->retired.end());
@@ -548,7 +553,10 @@ int WsSlot::aux(size_t dbytes, size_t hbytes, WsAux* out) {
     int rc = grow(w, &w->aws, &w->aws_bytes, dbytes < WS_AUX_HEAD ? WS_AUX_HEAD : dbytes, st, WS_AUX_ZERO,
                   "hipMalloc(aux workspace)");
     if (rc) return rc;
-    if (w->aws != before || w->aws_bytes != have) w->aux_state_ok = true;   // freshly zeroed
+    if (w->aws != before || w->aws_bytes != have) {                         // freshly zeroed
+        w->aux_state_ok = true;
+        w->aws_gen = ++g_aux_gen;
+    }
     if (w->hws_bytes < hbytes) {
         if (capturing(st)) return ws_set_msg("aux host scratch cannot grow while the stream captures a graph");
         hipError_t e = hipStreamSynchronize(st);
@@ -569,6 +577,7 @@ int WsSlot::aux(size_t dbytes, size_t hbytes, WsAux* out) {
     out->h = w->hws;
     out->h_dev = w->hws_dev;
     out->state_ok = &w->aux_state_ok;
+    out->gen = w->aws_gen;
     return 0;
 }
 
@@ -622,6 +631,17 @@ int WsSlot::advice(int** host, int** dev) {
 }
 
 bool ws_capturing(hipStream_t stream) { return capturing(stream); }
+
+// `base` is still the same allocation `gen` of some slot's auxiliary device scratch, of at least
+// `bytes` (the plan stats read a finished call's plan out of it; an address handed out again after a
+// free has another generation)
+bool ws_aux_alive(const void* base, size_t bytes, unsigned long long gen) {
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    for (auto& d : g_dev)
+        for (auto& w : d.sw)
+            if (w.aws && w.aws == base && w.aws_bytes >= bytes && w.aws_gen == gen) return true;
+    return false;
+}
 
 // per-call generation number for the piece path's disorder word (never 0)
 u32 ws_next_gen() {

@@ -315,6 +315,7 @@ struct WsAux {
     void* d;              // device scratch
     void* h;              // pinned host scratch (nullptr until requested)
     void* h_dev;          // its device address
+    unsigned long long gen;   // which allocation of the device scratch this is (ws_aux_alive)
     bool* state_ok;       // the owner's flag: the head holds a resting state
 };
 // The workspace slot of (HIP stream, graph capture), pinned for one call (ws_api.hip): every
@@ -337,6 +338,8 @@ struct WsSlot {
     int side(hipStream_t* side, hipEvent_t* ev, int prio);         // the raw stream's split walk: side stream + events
 };
 bool ws_capturing(hipStream_t stream);
+bool ws_aux_alive(const void* base, size_t bytes, unsigned long long gen);   // that allocation of a slot's aux scratch still lies at base (ws_api.hip)
+int ws_stream_plan_stat(const char* name, unsigned long long* value);   // stats "stream_plan_*" (ws_stream.hip)
 int ws_launch_piece(const WsLaunch& L, u64 lo, u64 hi, unsigned char* ws, u32 gen, int* advice,
                     const u32** disorder_out, bool* fallback_needed, u32 g0 = 0);
 // the batch decode with every segment inside [lo, hi) of buf (ws_api.hip); `ws`

@@ -18,10 +18,13 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "ws_common.h"
 #include "ws_link.h"
+#include "ws_rwplan.h"
 
 #define SPASS_T 256
 
@@ -392,41 +395,15 @@ __global__ __launch_bounds__(64) void ws_rw_chunk_kernel(const unsigned char* __
 //      (stream_walk from the chain's frame index), the last one also the tail, count and
 //      result.
 // Every byte decision is made by the reference rules; speculation only picks where to start.
-#define RW_CMAX (16ull << 20)
-#define RW_CMIN (64ull << 10)
-#define RW_HMAX (128u << 10)
-#define RW_HMIN (4u << 10)
-#define RW_SAMPLE (256ull << 10)
-// (the record pools RW_S0, RW_S1, RW_SLAST, the owners per chunk RW_D: ws_link.h)
+// (the record pools RW_S0, RW_S1, RW_SLAST, the owners per chunk RW_D: ws_link.h; the chunk, window,
+// sample and staging bounds RW_CMIN .. RW_STG and the thresholds RW_MIN, RW_MIN_FRAMES: ws_rwplan.h)
 #define RW_TPOS 64        // window positions per thread
-#define RW_STG 4096       // largest staging list per owner (frame offsets); the call's is stgn
-#define RW_MIN (512ull << 10)     // streams shorter than this after the passes: one wavefront walks
-#define RW_MIN_FRAMES 256         // ... and, after the sample, fewer frames than this (by the mean)
 // captured (device-planned) calls: R1 and R2 grid-stride grids, blocks of 256 (round 5: R1
 // 4096 -> 16384 blocks 176.8 -> 160.8 us, R2 4096 -> 8192 42.9 -> 36.9 us on cfg3,
 // profiles/r05_stream_grid_ab.log)
 #define RW_R1_GRID 16384
 #define RW_R2_GRID 8192
 #define RW_WCAP 256       // R1: candidates of a wave spread over its lanes (more: lane by lane)
-
-__host__ __device__ static u64 rw_pow2_clamp(u64 x, u64 lo, u64 hi) {
-    u64 v = lo;
-    while (v < x && v < hi) v <<= 1;
-    return v;
-}
-
-// The window at each chunk's start must hold a frame start of the chain: any window longer
-// than every frame does. 4 mean frames or the sample's longest frame + 4 KiB, whichever is
-// larger, in 4 KiB steps, within [RW_HMIN, min(C / 2, RW_HMAX)] (round 3: 8 mean frames
-// rounded up to a power of two; cfg3 128 -> 92 KiB, stream 8.32-8.36 -> 8.19 ms eager,
-// profiles/r04_stream_rw_ab.log)
-__device__ static u32 rw_window(u64 mean, u32 maxlen, u64 C) {
-    // (round 5: 0, 2 or 4 mean frames measured the same on one buffer, R1 unchanged at 247 us)
-    const u64 hi = C / 2 < RW_HMAX ? C / 2 : RW_HMAX;
-    u64 h = mean * 4 > (u64)maxlen + 4096 ? mean * 4 : (u64)maxlen + 4096;
-    h = (h + 4095) & ~4095ull;
-    return (u32)(h < RW_HMIN ? RW_HMIN : (h > hi ? hi : h));
-}
 
 // The walk's geometry chosen on the device (captured calls: the host cannot read the sample):
 // R1-R3, the linker and the emit take it from here; scratch is sized for the caps at capture.
@@ -435,15 +412,8 @@ __device__ static u32 rw_window(u64 mean, u32 maxlen, u64 C) {
 // short: it is the walk K2's first launch waits for), the last part = [B_last, len) in large
 // chunks, and (stream_split2) a middle part; the parts after part 0 are walked on a side stream
 // beside K2's launches over the earlier parts' pieces. Chunk arrays are indexed by the global
-// chunk g = cbase + local index; per-part lists start at their bases.
-struct RwPart {
-    u64 P;                // the part's chunk grid origin
-    u64 C;                // its chunk bytes
-    u32 H, n, cbase, capc; // window bytes, chunks, first global chunk, candidates per chunk
-    u32 stgn, pad;        // staging per owner
-    u64 stg_base, cand_base;  // where its staging and candidate lists start (entries)
-};
-#define RW_NP 3           // parts of a split walk at most
+// chunk g = cbase + local index; per-part lists start at their bases. The arithmetic itself — C, H,
+// the parts (RwPart), their counts and bases — is rw_plan_geometry (ws_rwplan.h).
 struct RwPlan {
     RwPart pt[RW_NP];     // parts past nparts empty (n = 0)
     u32 nchunks;          // sum of the parts' chunks (global chunk count)
@@ -456,6 +426,9 @@ struct RwPlan {
     u64 in_ent[RW_NP];
     u32 in_nf[RW_NP], in_state[RW_NP];
     u32 nw[RW_NP];        // the item count K2's launch k reads (k < nparts - 1): every item it may need is written
+    // what the serial linker did in each part (read back by the plan stats, never by a kernel): 1 if it
+    // ran (the parallel one did not link the part), and the chunks it walked itself for want of a record
+    u32 lk_serial[RW_NP], lk_walks[RW_NP];
 };
 static_assert(sizeof(RwPlan) <= WS_AUX_ZERO - WS_AUX_HEAD, "RwPlan lies in the zeroed aux range (WS_AUX_ZERO)");
 
@@ -769,9 +742,7 @@ __global__ __launch_bounds__(64) void ws_rw_emit_kernel(const unsigned char* __r
 // ---- the chunk-parallel walk inside a captured call (no host reads): the plan kernel
 // walks the sample and picks the geometry, R1-R3 read it, the linker follows the records
 // on the device (the host loop of rw_walk, one wavefront), the emit writes the chain.
-#define RW_CAP_CHUNKS 32768u   // a captured call's chunk-count cap (the smallest chunk follows)
-#define RW_CAP_STGN 1024u      // ... and staging per owner
-
+// (RW_CAP_CHUNKS, a device-planned call's chunk-count cap, and RW_CAP_STGN, its staging per owner: ws_rwplan.h)
 __global__ __launch_bounds__(64) void ws_rw_plan_kernel(const unsigned char* __restrict__ buf, u64 len, u32 max_frames,
                                                         SdState* __restrict__ sd, RwPlan* __restrict__ plan,
                                                         u64 cmin, u64 cmax, u32 nchunks_cap, u64 cand_cap, u64 stg_cap,
@@ -830,95 +801,39 @@ __global__ __launch_bounds__(64) void ws_rw_plan_kernel(const unsigned char* __r
         return;
     }
     const u64 P1 = o.next;
-    const u64 mean = o.nf > nf ? (P1 - P) / (o.nf - nf) : (P1 - P);
-    if ((len - P1) / (mean ? mean : 1) < RW_MIN_FRAMES) {                   // a short rest: this wavefront
+    const u64 mean = rw_sample_mean(P, P1, o.nf - nf);
+    if (rw_short_rest(P1, len, mean)) {                                      // a short rest: this wavefront
         const SwOut o3 = stream_walk(buf, len, P1, 0, o.nf, len, true, max_frames, desc, items, ptr, pend, nwork, res,
                                      lane);
         finished(o3.cnt);
         return;
     }
-    const u32 seenm = o.maxlen > seen ? o.maxlen : seen;
-    u64 C = rw_pow2_clamp(mean * 1024, cmin > RW_CMIN ? cmin : RW_CMIN, cmin > cmax ? cmin : cmax);
-    // split (split_x0 / split_x1: the first bytes K2's second / third launch own; 0 = none): part k
-    // ends at the first chunk start at or past split_x_k; part 0's chunks are C >> c0_shift, a middle
-    // part's C >> c1_shift (at least twice the window a frame start needs), the last part's C
-    const u64 hneed = rw_window(mean, seenm, 4 * (u64)RW_HMAX);
-    const u64 xs[RW_NP - 1] = {split_x0, split_x1};
-    const u32 shifts[RW_NP - 1] = {c0_shift, c1_shift};
-    u64 Pk[RW_NP], Ck[RW_NP], nk[RW_NP];
-    u32 np = 1;
-    for (;;) {
-        u64 B = P1, tot = 0;
-        np = 0;
-        for (u32 k = 0; k < RW_NP; ++k) {
-            const bool lastp = k + 1 == RW_NP || !xs[k] || xs[k] >= len;
-            u64 Cx = C;
-            if (!lastp) {
-                const u64 want = (C >> shifts[k]) > 2 * hneed ? (C >> shifts[k]) : 2 * hneed;
-                Cx = rw_pow2_clamp(want, RW_CMIN, C);
-            }
-            u64 E = len;
-            if (!lastp) {
-                E = xs[k] > B ? B + (xs[k] - B + Cx - 1) / Cx * Cx : B;
-                if (E >= len) E = len;
-            }
-            Pk[k] = B; Ck[k] = Cx; nk[k] = E > B ? (E - B + Cx - 1) / Cx : 0;
-            tot += nk[k];
-            ++np;
-            B = E;
-            if (lastp || E >= len) break;
-        }
-        // fit the caps (cmin makes the chunk count fit; the smallest staging and candidate lists too)
-        if (tot <= nchunks_cap && tot * RW_D * 64 <= stg_cap && tot * 64 <= cand_cap) break;
-        C <<= 1;
-    }
-    u64 Hk[RW_NP], stgk[RW_NP], capk[RW_NP];
-    u64 stg_need = 0, cand_need = 0;
-    for (u32 k = 0; k < np; ++k) {
-        Hk[k] = rw_window(mean, seenm, Ck[k]);
-        stgk[k] = rw_pow2_clamp(2 * Ck[k] / (mean ? mean : 1), 256, RW_CAP_STGN);
-        capk[k] = Hk[k] / 32;
-    }
-    for (;;) {                                                               // shrink staging / candidates to the caps
-        stg_need = cand_need = 0;
-        bool can = false;
-        for (u32 k = 0; k < np; ++k) {
-            stg_need += nk[k] * RW_D * stgk[k];
-            cand_need += nk[k] * capk[k];
-            can = can || stgk[k] > 64 || capk[k] > 64;
-        }
-        if ((stg_need <= stg_cap && cand_need <= cand_cap) || !can) break;
-        for (u32 k = 0; k < np; ++k) {
-            if (stg_need > stg_cap && stgk[k] > 64) stgk[k] >>= 1;
-            if (cand_need > cand_cap && capk[k] > 64) capk[k] >>= 1;
-        }
-    }
+    // the geometry (ws_rwplan.h): split_x0 / split_x1 are the first bytes K2's second / third launch own
+    // (0 = none); every lane computes the same
+    RwPlanIn in;
+    in.P1 = P1; in.len = len; in.mean = mean; in.longest = o.maxlen > seen ? o.maxlen : seen;
+    in.cmin = cmin; in.cmax = cmax; in.nchunks_cap = nchunks_cap; in.cand_cap = cand_cap; in.stg_cap = stg_cap;
+    in.split_x[0] = split_x0; in.split_x[1] = split_x1; in.shift[0] = c0_shift; in.shift[1] = c1_shift;
+    const RwGeom G = rw_plan_geometry(in);
     if (lane == 0) {
-        u64 cb = 0, sb = 0, cdb = 0;
         for (u32 k = 0; k < RW_NP; ++k) {
-            RwPart& t = plan->pt[k];
-            if (k < np) {
-                t.P = Pk[k]; t.C = Ck[k]; t.H = (u32)Hk[k]; t.n = (u32)nk[k]; t.cbase = (u32)cb; t.capc = (u32)capk[k];
-                t.stgn = (u32)stgk[k]; t.stg_base = sb; t.cand_base = cdb;
-                cb += nk[k]; sb += nk[k] * RW_D * stgk[k]; cdb += nk[k] * capk[k];
-            } else {
-                t.P = len; t.C = C; t.H = RW_HMIN; t.n = 0; t.cbase = (u32)cb; t.capc = 64; t.stgn = 64;
-                t.stg_base = sb; t.cand_base = cdb;
-            }
+            plan->pt[k] = G.pt[k];
             plan->nrows[k] = 0;
             plan->linked[k] = 0;
             plan->in_ent[k] = 0;
             plan->in_nf[k] = 0;
             plan->in_state[k] = 0;
             plan->nw[k] = 0;
+            plan->lk_serial[k] = 0;
+            plan->lk_walks[k] = 0;
         }
-        plan->nchunks = (u32)cb;
-        plan->nparts = np;
+        plan->nchunks = G.nchunks;
+        plan->nparts = G.nparts;
         plan->need_mask = (buf[P1 + 1] & 0x80u) ? 1u : 0u;                   // client frames: masked
         plan->nf = o.nf;
         plan->seen_max = 0;                 // this call's emit and linker fill it in
         plan->active = 1;
-        rw_end_states(plan, (int)np - 1);   // parts past the last one are no-ops
+        rw_end_states(plan, (int)G.nparts - 1);   // parts past the last one are no-ops
     }
 }
 
@@ -1103,7 +1018,7 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
     // moves to the next chunk), then taken one chunk at a time; a chain that leaves that run
     // (a skipped chunk, a chunk walked here) reloads at its new chunk.
     constexpr u32 RW_LK = 8;
-    u32 steps = 0, mx = 0;
+    u32 steps = 0, mx = 0, walks = 0;
     while (!last && ent < len && steps <= np + 1 && !(has_next && ent >= Pb)) {
         const u64 c0 = (ent - P) / C;                                        // local chunk
         // lane l < RW_LK: the record counts of chunk c0 + l (read back per chunk by readlane)
@@ -1152,6 +1067,7 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
                 continue;
             }
             // no usable record: this wavefront walks the chunk (writing its frames)
+            ++walks;
             const SwOut o = stream_walk(buf, len, ent, 0, nfc, cs0 + C < len ? cs0 + C : len, false, max_frames, desc,
                                         items, ptr, pend, nwork, res, lane, plan->sample_out, true);
             if (o.maxlen > mx) mx = o.maxlen;
@@ -1173,6 +1089,8 @@ __global__ __launch_bounds__(64) void ws_rw_link_kernel(const unsigned char* __r
     rw_note_max(plan, mx, lane);
     if (lane == 0) {
         plan->nrows[part] = rows;
+        plan->lk_serial[part] = 1;
+        plan->lk_walks[part] = walks;
         if (handoff) {
             rw_hand_over(plan, part, ent, nfc);
         } else {
@@ -1212,6 +1130,76 @@ WsOpt ws_stream_c0{3};          // "stream_c0": part 0's chunks are the usual ch
 std::atomic<unsigned long long> ws_stat_rw_chunks{0};       // chunks written from records (last call)
 std::atomic<unsigned long long> ws_stat_stream_skips{0};    // eager calls that skipped the pass rounds (since load)
 std::atomic<unsigned long long> ws_stat_rw_chunk_walks{0};  // chunks walked by one wavefront without a record
+
+// The plan of this process's last chunk-planned raw-stream call, for the stats "stream_plan_*"
+// (websocketframeGpuGetStat): a device-planned call leaves where its RwPlan lies (read back by the
+// getter, after a device synchronize, while that workspace lives), a host-linked call the values the
+// host chose. Nothing is launched or written on the device for it.
+struct RwLastPlan {
+    int path = 0;                    // 0 none yet, 1 device-planned, 2 host-linked
+    int dev = 0;                     // device-planned: the device, the aux workspace's base, the plan in it
+    const void* aux = nullptr;
+    unsigned long long gen = 0;
+    const RwPlan* plan = nullptr;
+    RwPlan host = {};                // host-linked: one part, filled in by rw_walk
+};
+static RwLastPlan g_rw_last;
+static std::mutex g_rw_last_mu;
+
+static void rw_note_device_plan(const void* aux, unsigned long long gen, const RwPlan* plan) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(g_rw_last_mu);
+    g_rw_last.path = 1;
+    g_rw_last.dev = dev;
+    g_rw_last.aux = aux;
+    g_rw_last.gen = gen;
+    g_rw_last.plan = plan;
+}
+
+// name: what follows "stream_plan_" — path, nparts, nchunks, active, nf, or a part's field and the
+// part's digit (P0, C1, H2, n0, capc0, stgn0, nrows0, linked0, in_ent1, in_nf1, in_state1, lk_serial0,
+// lk_walks0). -1: no such call yet, its workspace is gone, or no such name.
+int ws_stream_plan_stat(const char* name, unsigned long long* value) {
+    std::lock_guard<std::mutex> lk(g_rw_last_mu);
+    if (!g_rw_last.path) return -1;
+    RwPlan pl = g_rw_last.host;
+    if (g_rw_last.path == 1) {
+        if (!ws_aux_alive(g_rw_last.aux, WS_AUX_HEAD + sizeof(RwPlan), g_rw_last.gen)) return -1;
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess) return -1;
+        if (cur != g_rw_last.dev && hipSetDevice(g_rw_last.dev) != hipSuccess) return -1;
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(&pl, g_rw_last.plan, sizeof(RwPlan), hipMemcpyDeviceToHost);
+        if (cur != g_rw_last.dev) (void)hipSetDevice(cur);
+        if (e != hipSuccess) return -1;
+    }
+    if (!strcmp(name, "path")) { *value = (unsigned long long)g_rw_last.path; return 0; }
+    if (!strcmp(name, "nparts")) { *value = pl.nparts; return 0; }
+    if (!strcmp(name, "nchunks")) { *value = pl.nchunks; return 0; }
+    if (!strcmp(name, "active")) { *value = pl.active; return 0; }
+    if (!strcmp(name, "nf")) { *value = pl.nf; return 0; }
+    const size_t n = strlen(name);
+    if (n < 2 || name[n - 1] < '0' || name[n - 1] >= '0' + RW_NP) return -1;
+    const int k = name[n - 1] - '0';
+    auto is = [&](const char* f) { return strlen(f) == n - 1 && !strncmp(name, f, n - 1); };
+    const RwPart& t = pl.pt[k];
+    if (is("P")) *value = t.P;
+    else if (is("C")) *value = t.C;
+    else if (is("H")) *value = t.H;
+    else if (is("n")) *value = t.n;
+    else if (is("capc")) *value = t.capc;
+    else if (is("stgn")) *value = t.stgn;
+    else if (is("nrows")) *value = pl.nrows[k];
+    else if (is("linked")) *value = pl.linked[k];
+    else if (is("in_ent")) *value = pl.in_ent[k];
+    else if (is("in_nf")) *value = pl.in_nf[k];
+    else if (is("in_state")) *value = pl.in_state[k];
+    else if (is("lk_serial")) *value = pl.lk_serial[k];
+    else if (is("lk_walks")) *value = pl.lk_walks[k];
+    else return -1;
+    return 0;
+}
 
 // scratch for the chunk-parallel walk: the call's slot's auxiliary workspace (device
 // records + counters, and a pinned host copy of them), so concurrent calls on different
@@ -1268,10 +1256,21 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     u32 nf1 = 0;
     if ((rc = chunk_walk(P, nf, P + RW_SAMPLE, P1, nf1))) return rc < 0 ? rc : 0;
     ws_stat_rw_chunk_walks = 0;                                              // not counting the sample
-    const u64 mean = nf1 > nf ? (P1 - P) / (nf1 - nf) : (P1 - P);
+    const u64 mean = rw_sample_mean(P, P1, nf1 - nf);
     P = P1;
     nf = nf1;
-    if ((len - P) / (mean ? mean : 1) < RW_MIN_FRAMES) {                    // a short rest: one wavefront
+    RwPlan hp = {};                                                          // what the plan stats read
+    hp.nparts = 1;
+    hp.nf = nf;
+    hp.pt[0].P = P;
+    for (int k = 1; k < RW_NP; ++k) hp.pt[k].P = len;
+    auto note_plan = [&]() {
+        std::lock_guard<std::mutex> lk(g_rw_last_mu);
+        g_rw_last.path = 2;
+        g_rw_last.host = hp;
+    };
+    if (rw_short_rest(P, len, mean)) {                                       // a short rest: one wavefront
+        note_plan();
         hipLaunchKernelGGL(ws_stream_walk_kernel, dim3(1), dim3(64), 0, st, d_buf, len, P, (u64)0, nf, max_frames,
                            d_desc, Pw.items, Pw.ptr, Pw.npieces, Pw.nwork, d_res);
         if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_stream_walk_kernel launch", e);
@@ -1279,18 +1278,16 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     }
     const int cmax_log = ws_stream_rw_cmax;                                  // one read per call
     const u64 cmax = cmax_log >= 16 && cmax_log <= 26 ? 1ull << cmax_log : RW_CMAX;
-    const u64 C = rw_pow2_clamp(mean * 1024, RW_CMIN, cmax);
-    const u32 H = (u32)rw_pow2_clamp(mean * 8, RW_HMIN, C / 2 < RW_HMAX ? C / 2 : RW_HMAX);
-    const u64 nchunks = (len - P + C - 1) / C;
+    const RwHostGeom HG = rw_host_geometry(P, len, mean, cmax);              // (ws_rwplan.h)
+    const u64 C = HG.C, nchunks = HG.nchunks;
+    const u32 H = HG.H, stgn = HG.stgn, capc = HG.capc;
     const size_t b_recs = ((size_t)(nchunks * RW_SLOTS + RW_SLAST) * sizeof(RwRec) + 255) & ~(size_t)255;
     const size_t b_nrec = ((size_t)nchunks * 16 + 255) & ~(size_t)255;     // per chunk: n0, n1, candidates
     const size_t b_dx = ((size_t)nchunks * RW_D * 8 + 255) & ~(size_t)255;
     const size_t b_own = ((size_t)nchunks * RW_D * sizeof(RwOwn) + 255) & ~(size_t)255;
     const size_t b_tab = ((size_t)nchunks * sizeof(RwRow) + 255) & ~(size_t)255;
     // staging: about twice the chunk's mean frame count (frames past it are walked by the emit)
-    const u32 stgn = (u32)rw_pow2_clamp(2 * C / (mean ? mean : 1), 256, RW_STG);
     const size_t b_stg = (size_t)nchunks * RW_D * stgn * 4;
-    const u32 capc = H / 32;                                                 // candidates: 1/32 of a window
     const size_t b_cand = (size_t)nchunks * capc * 8;
     const size_t b_host = b_recs + b_nrec + b_dx + 256 + b_own;              // copied back
     if ((rc = rw_scratch(slot, 256 + b_host + b_tab + b_stg + b_cand, 256 + b_host, &S))) return rc;
@@ -1371,6 +1368,15 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     }
     const u32 nblk = (u32)ht.size();
     ws_stat_rw_chunks = nblk;
+    hp.active = 1;
+    hp.nchunks = (u32)nchunks;
+    hp.need_mask = need_mask;
+    hp.pt[0].C = C; hp.pt[0].H = H; hp.pt[0].n = (u32)nchunks; hp.pt[0].capc = capc; hp.pt[0].stgn = stgn;
+    hp.nrows[0] = nblk;
+    hp.linked[0] = 1;
+    hp.lk_serial[0] = 1;
+    hp.lk_walks[0] = (u32)ws_stat_rw_chunk_walks.load();
+    note_plan();
     if (nblk) {
         if ((e = hipMemcpyAsync(tab, ht.data(), ht.size() * sizeof(RwRow), hipMemcpyHostToDevice, st)) != hipSuccess)
             return ws_set_err("hipMemcpyAsync(stream chain)", e);
@@ -1429,9 +1435,10 @@ struct RwSplit {
 
 static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, WebsocketFrameDesc_t* d_desc,
                           const PieceWs& Pw, WebsocketSegResult_t* d_res, hipStream_t st, SdState* sd,
-                          unsigned char* w, const RwDevLayout& L, int fresh = 0, u64* d_seg = nullptr,
+                          unsigned char* w, const RwDevLayout& L, unsigned long long aux_gen, int fresh = 0, u64* d_seg = nullptr,
                           SdMirror* mirror = nullptr, const RwSplit* sp = nullptr) {
     RwPlan* plan = reinterpret_cast<RwPlan*>(w + L.o_plan);
+    rw_note_device_plan(w - WS_AUX_HEAD, aux_gen, plan);                     // (host words only: the plan stats)
     u32* nrec = reinterpret_cast<u32*>(w + L.o_nrec);
     unsigned long long* dx = reinterpret_cast<unsigned long long*>(w + L.o_dx);
     RwRec* recs = reinterpret_cast<RwRec*>(w + L.o_recs);
@@ -1653,7 +1660,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
         // a replay whose previous replay's chunk walk saw lengths that keep changing skips the
         // rounds on the device (they exit at once) and the plan kernel starts the walk at 0
         if ((rc = rounds(nr, false, 0, 1))) return rc;
-        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, 2, d_seg, nullptr, &SP)))
+        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 2, d_seg, nullptr, &SP)))
             return rc;
         *A.state_ok = true;
         return rw_unmask(L, Pw, gen, &SP, rw_plan);
@@ -1684,7 +1691,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     if (rw_opt == 1 && __atomic_load_n(&hm->walk_hint, __ATOMIC_RELAXED) == 1) {
         ++ws_stat_stream_skips;
         *A.state_ok = true;
-        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, 1, d_seg, dm, &SP)))
+        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 1, d_seg, dm, &SP)))
             return rc;
         return rw_unmask(L, Pw, gen, &SP, rw_plan);
     }
@@ -1699,7 +1706,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
         const u64 P = hm->P;
         const u32 nf = hm->nf;
         if (len - P >= RW_MIN && rw_opt == 1) {                              // lengths keep changing:
-            if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, 0, d_seg, dm,
+            if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 0, d_seg, dm,
                                      &SP)))                                  // the device walks
                 return rc;
             return rw_unmask(L, Pw, gen, &SP, rw_plan);
