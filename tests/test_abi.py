@@ -262,3 +262,64 @@ def test_documented_options_are_accepted():
     r = subprocess.run([os.environ.get("PYTHON", "python3"), "-c", OPTION_CHECK, _lib.REPO, ",".join(names)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+# name: (lo, hi, default), written out from the setter's range checks as they stood before the option
+# table (not read from the library); None: no range
+OPTION_RANGES = {
+    "path": (-1, 4, -1), "host_chunk_mb": (1, 65536, 64), "piece_lds": (0, 65536, 0), "piece_win": (-1, 6, -1),
+    "seg_win": (-1, 3, -1), "reasm_path": (0, 2, 0), "reasm_cfg": (0, 2, 0), "enc_front": (0, 1, 1),
+    "stream_rw": (0, 2, 1), "stream_rw_cmax": (16, 26, 22), "stream_plink": (0, 1, 1), "stream_split": (0, 255, 8),
+    "stream_split_wait": (0, 2, 0), "stream_split2": (0, 255, 48), "stream_win": (-1, 6, 2),
+    "stream_split_capture": (0, 1, 1), "stream_c1": (0, 6, 2), "stream_side_prio": (0, 2, 0), "stream_c0": (0, 6, 3),
+    "stream_rounds": (1, 64, 4), "scan_alpha": (0, 1, 1), "k2_timing": (None, None, 0),
+}
+
+RANGE_CHECK = r"""
+import ctypes as C, json, sys
+sys.path.insert(0, sys.argv[1])
+from util_amd import wsframe as W
+lib = W.load_lib()
+set_ = lib.websocketframeGpuSetOption
+set_.restype, set_.argtypes = C.c_int, [C.c_char_p, C.c_longlong]
+stat = lib.websocketframeGpuGetStat
+stat.restype, stat.argtypes = C.c_int, [C.c_char_p, C.c_void_p]
+bad = []
+ranges = json.loads(sys.argv[2])
+for name, (lo, hi, default) in sorted(ranges.items()):
+    n = name.encode()
+    if lo is None:                                        # k2_timing: every value is taken
+        want = [(-5, 0), (0, 0), (1, 0), (1 << 40, 0)]
+    else:
+        want = [(lo, 0), (hi, 0), (lo - 1, -1), (hi + 1, -1)]
+    if name == "path":
+        want += [(0, -1), (2, -1), (1, 0), (3, 0)]
+    bad += [(name, v, rc) for v, rc in want if set_(n, v) != rc]
+    if set_(n, default) != 0:
+        bad.append((name, "default", default))
+if set_(b"no_such_option", 1) != -1:
+    bad.append("unknown option accepted")
+v = C.c_ulonglong(7)
+if stat(b"no_such_stat", C.byref(v)) != -1 or v.value != 7:
+    bad.append("unknown stat")
+if stat(b"stream_skips", None) != -1 or stat(b"k2_ns", None) != -1:
+    bad.append("NULL value pointer")
+if stat(b"stream_skips", C.byref(v)) != 0 or v.value != 0:
+    bad.append("a counter of a fresh process")
+print("BAD", bad)
+sys.exit(1 if bad else 0)
+"""
+
+
+def test_option_ranges_and_unknown_names():
+    """the ends of every option's range are accepted and the values just outside refused ("path": the set
+    {-1, 1, 3, 4}); unknown option and stat names and a NULL value pointer give -1; the table names exactly
+    the header's knobs. A child process that never touches the GPU; it puts every default back."""
+    import json
+    hdr = open(os.path.join(_lib.REPO, "include", "wsframe_amd.h")).read()
+    block = hdr[hdr.index("/* Launch tuning knobs"):hdr.index("WSFRAME_AMD_EXPORT int websocketframeGpuSetOption")]
+    assert sorted(OPTION_RANGES) == sorted(set(re.findall(r'"([a-z0-9_]+)"', block)))
+    util_amd.load_lib()
+    r = subprocess.run([os.environ.get("PYTHON", "python3"), "-c", RANGE_CHECK, _lib.REPO, json.dumps(OPTION_RANGES)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr

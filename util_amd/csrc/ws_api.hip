@@ -21,28 +21,8 @@
 #include "ws_common.h"
 
 static __thread char g_last_error[256];
-extern std::atomic<size_t> ws_host_chunk_bytes;
-extern WsOpt ws_reasm_path;
-extern WsOpt ws_reasm_cfg;
-extern WsOpt ws_piece_lds;
-extern WsOpt ws_piece_win;
-extern WsOpt ws_k2_timing;
-void ws_k2_timing_reset();
-int ws_k2_stat(unsigned long long* ns, unsigned long long* calls);
-extern WsOpt ws_enc_front;
-extern WsOpt ws_scan_alpha;
 WsOpt ws_seg_win{-1};     // "seg_win": segfuse and fused reassembly take segments in 2^seg_win windows (ws_winn);
                           // -1: 4 windows for segfuse, 8 for the fused reassembly (profiles/r06_seg_win_ab.log)
-extern WsOpt ws_stream_rw, ws_stream_rw_cmax, ws_stream_rounds, ws_stream_plink;
-extern WsOpt ws_stream_win, ws_stream_split_capture, ws_stream_split, ws_stream_split_wait, ws_stream_c0, ws_stream_side_prio, ws_stream_split2,
-    ws_stream_c1;
-size_t ws_workspace_bytes_total();
-extern std::atomic<unsigned long long> ws_stat_rw_chunks, ws_stat_rw_chunk_walks, ws_stat_stream_skips,
-    ws_stat_stream_splits;
-extern std::atomic<unsigned long long> ws_stat_host_groups;
-extern std::atomic<unsigned long long> ws_stat_adoptions;
-extern std::atomic<unsigned long long> ws_stat_k2_windows;
-extern std::atomic<unsigned long long> ws_stat_adoption_refusals;
 
 int ws_set_err(const char* what, hipError_t e) {
     snprintf(g_last_error, sizeof(g_last_error), "%s: %s", what, hipGetErrorString(e));
@@ -63,98 +43,52 @@ extern "C" WSFRAME_AMD_EXPORT const char* websocketframeGpuLastError(void) { ret
 static WsOpt g_path{-1};   // "path": -1 auto (4 for many small segments, else 3), 1 walker (one wave per
                            // segment), 3 piece (K1 + K2), 4 segfuse
 
+// every option that is a plain integer range: the setter refuses a value outside [lo, hi], and each
+// initialiser lies inside, so a reader needs no check of its own
+static const struct { const char* name; WsOpt* opt; int lo, hi; } g_options[] = {
+    {"piece_lds", &ws_piece_lds, 0, 65536}, {"piece_win", &ws_piece_win, -1, 6},
+    {"seg_win", &ws_seg_win, -1, 3}, {"scan_alpha", &ws_scan_alpha, 0, 1},
+    {"reasm_path", &ws_reasm_path, 0, 2}, {"reasm_cfg", &ws_reasm_cfg, 0, 2},
+    {"enc_front", &ws_enc_front, 0, 1},
+    {"stream_rw", &ws_stream_rw, 0, 2}, {"stream_rw_cmax", &ws_stream_rw_cmax, 16, 26},
+    {"stream_rounds", &ws_stream_rounds, 1, 64}, {"stream_plink", &ws_stream_plink, 0, 1},
+    {"stream_split", &ws_stream_split, 0, 255}, {"stream_split2", &ws_stream_split2, 0, 255},
+    {"stream_split_wait", &ws_stream_split_wait, 0, 2}, {"stream_split_capture", &ws_stream_split_capture, 0, 1},
+    {"stream_c0", &ws_stream_c0, 0, 6}, {"stream_c1", &ws_stream_c1, 0, 6},
+    {"stream_win", &ws_stream_win, -1, 6}, {"stream_side_prio", &ws_stream_side_prio, 0, 2},
+};
+
 extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuSetOption(const char* name, long long value) {
-    if (!strcmp(name, "path")) {
+    if (!strcmp(name, "path")) {                                       // a set, not a range
         if (value != -1 && value != 1 && value != 3 && value != 4) return -1;
         g_path = (int)value;
+        return 0;
     }
-    else if (!strcmp(name, "host_chunk_mb")) {
+    if (!strcmp(name, "host_chunk_mb")) {                              // a size_t, in bytes
         if (value <= 0 || value > 65536) return -1;
         ws_host_chunk_bytes = (size_t)value << 20;
+        return 0;
     }
-    else if (!strcmp(name, "piece_lds")) {
-        if (value < 0 || value > 65536) return -1;
-        ws_piece_lds = (int)value;
-    }
-    else if (!strcmp(name, "piece_win")) {
-        if (value < -1 || value > 6) return -1;
-        ws_piece_win = (int)value;
-    }
-    else if (!strcmp(name, "seg_win")) {
-        if (value < -1 || value > 3) return -1;
-        ws_seg_win = (int)value;
-    }
-    else if (!strcmp(name, "reasm_path")) {
-        if (value < 0 || value > 2) return -1;
-        ws_reasm_path = (int)value;
-    }
-    else if (!strcmp(name, "reasm_cfg")) {
-        if (value < 0 || value > 2) return -1;
-        ws_reasm_cfg = (int)value;
-    }
-    else if (!strcmp(name, "enc_front")) {
-        if (value < 0 || value > 1) return -1;
-        ws_enc_front = (int)value;
-    }
-    else if (!strcmp(name, "stream_rw")) {
-        if (value < 0 || value > 2) return -1;
-        ws_stream_rw = (int)value;
-    }
-    else if (!strcmp(name, "stream_rw_cmax")) {
-        if (value < 16 || value > 26) return -1;
-        ws_stream_rw_cmax = (int)value;
-    }
-    else if (!strcmp(name, "stream_plink")) {
-        if (value < 0 || value > 1) return -1;
-        ws_stream_plink = (int)value;
-    }
-    else if (!strcmp(name, "stream_split")) {
-        if (value < 0 || value > 255) return -1;
-        ws_stream_split = (int)value;
-    }
-    else if (!strcmp(name, "stream_split_wait")) {
-        if (value < 0 || value > 2) return -1;
-        ws_stream_split_wait = (int)value;
-    }
-    else if (!strcmp(name, "stream_split2")) {
-        if (value < 0 || value > 255) return -1;
-        ws_stream_split2 = (int)value;
-    }
-    else if (!strcmp(name, "stream_win")) {
-        if (value < -1 || value > 6) return -1;
-        ws_stream_win = (int)value;
-    }
-    else if (!strcmp(name, "stream_split_capture")) {
-        if (value < 0 || value > 1) return -1;
-        ws_stream_split_capture = (int)value;
-    }
-    else if (!strcmp(name, "stream_c1")) {
-        if (value < 0 || value > 6) return -1;
-        ws_stream_c1 = (int)value;
-    }
-    else if (!strcmp(name, "stream_side_prio")) {
-        if (value < 0 || value > 2) return -1;
-        ws_stream_side_prio = (int)value;
-    }
-    else if (!strcmp(name, "stream_c0")) {
-        if (value < 0 || value > 6) return -1;
-        ws_stream_c0 = (int)value;
-    }
-    else if (!strcmp(name, "stream_rounds")) {
-        if (value < 1 || value > 64) return -1;
-        ws_stream_rounds = (int)value;
-    }
-    else if (!strcmp(name, "scan_alpha")) {
-        if (value < 0 || value > 1) return -1;
-        ws_scan_alpha = (int)value;
-    }
-    else if (!strcmp(name, "k2_timing")) {
+    if (!strcmp(name, "k2_timing")) {                                  // any value: on / off, and a fresh record
         ws_k2_timing = value ? 1 : 0;
         ws_k2_timing_reset();
+        return 0;
     }
-    else return -1;
-    return 0;
+    for (const auto& o : g_options) {
+        if (strcmp(name, o.name)) continue;
+        if (value < o.lo || value > o.hi) return -1;
+        *o.opt = (int)value;
+        return 0;
+    }
+    return -1;
 }
+
+static const struct { const char* name; std::atomic<unsigned long long>* stat; } g_stats[] = {
+    {"stream_rw_chunks", &ws_stat_rw_chunks}, {"stream_rw_chunk_walks", &ws_stat_rw_chunk_walks},
+    {"stream_skips", &ws_stat_stream_skips}, {"stream_splits", &ws_stat_stream_splits},
+    {"capture_adoptions", &ws_stat_adoptions}, {"capture_adoption_refusals", &ws_stat_adoption_refusals},
+    {"k2_windows", &ws_stat_k2_windows}, {"host_groups", &ws_stat_host_groups},
+};
 
 extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, unsigned long long* value) {
     if (!value) return -1;
@@ -165,18 +99,16 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, uns
         return 0;
     }
     if (!strncmp(name, "stream_plan_", 12)) return ws_stream_plan_stat(name + 12, value);
-    if (!strcmp(name, "stream_rw_chunks")) *value = ws_stat_rw_chunks.load();
-    else if (!strcmp(name, "stream_rw_chunk_walks")) *value = ws_stat_rw_chunk_walks.load();
-    else if (!strcmp(name, "stream_skips")) *value = ws_stat_stream_skips.load();
-    else if (!strcmp(name, "stream_splits")) *value = ws_stat_stream_splits.load();
-    else if (!strcmp(name, "workspace_bytes")) *value = ws_workspace_bytes_total();
-    else if (!strcmp(name, "capture_adoptions")) *value = ws_stat_adoptions.load();
-    else if (!strcmp(name, "k2_windows")) *value = ws_stat_k2_windows.load();
-    else if (!strcmp(name, "capture_adoption_refusals")) *value = ws_stat_adoption_refusals.load();
-    else if (!strcmp(name, "host_groups")) *value = ws_stat_host_groups.load();
-
-    else return -1;
-    return 0;
+    if (!strcmp(name, "workspace_bytes")) {
+        *value = ws_workspace_bytes_total();
+        return 0;
+    }
+    for (const auto& s : g_stats) {
+        if (strcmp(name, s.name)) continue;
+        *value = s.stat->load();
+        return 0;
+    }
+    return -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -189,6 +121,13 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeGpuGetStat(const char* name, uns
 // next eager library call frees its buffers (or the next capture adopts them, slot_rezero).
 #define WS_MAX_DEV 64
 #define WS_STREAM_SLOTS 16
+struct WsBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+static const char* const g_buf_what[WS_BUF_KINDS] = {"hipMalloc(workspace)", "hipMalloc(encode workspace)",
+                                                     "hipMalloc(text workspace)", "hipMalloc(protocol check workspace)",
+                                                     "hipMalloc(aux workspace)"};
 struct WsStreamWs {
     hipStream_t stream = nullptr;
     unsigned long long capture = 0; // capture id of the graph this slot belongs to (0: eager calls)
@@ -197,16 +136,7 @@ struct WsStreamWs {
     std::atomic<int> dead{0};      // its graph was destroyed (set by the user object's destructor)
     int busy = 0;                  // calls holding the slot (WsSlot)
     unsigned long long last = 0;   // LRU tick
-    u32* ws = nullptr;             // decode / reassembly / stream workspace
-    size_t ws_bytes = 0;
-    void* ews = nullptr;           // encode workspace (scan temp + piece pointers)
-    size_t ews_bytes = 0;
-    void* tws = nullptr;           // text validation workspace (ws_utf8.hip: per-slot records + tile scan)
-    size_t tws_bytes = 0;
-    void* pws = nullptr;           // protocol check workspace (ws_proto.hip: segment offsets + tile summaries)
-    size_t pws_bytes = 0;
-    void* aws = nullptr;           // auxiliary device scratch (the stream path's chunk-parallel walk)
-    size_t aws_bytes = 0;
+    WsBuf buf[WS_BUF_KINDS];       // the grow-on-demand device buffers (WsBufKind)
     unsigned long long aws_gen = 0; // which allocation (or adoption) of the aux scratch this is: never reused
     void* hws = nullptr;           // ... and its pinned host copy
     void* hws_dev = nullptr;       // (its device address)
@@ -237,7 +167,7 @@ size_t ws_workspace_bytes_total() {
     size_t t = 0;
     for (auto& d : g_dev) {
         for (auto& w : d.sw) {
-            t += w.ws_bytes + w.ews_bytes + w.aws_bytes + w.tws_bytes + w.pws_bytes;
+            for (auto& b : w.buf) t += b.bytes;
             for (auto& r : w.retired) t += r.second;
         }
         for (auto& r : d.deferred) t += r.second;
@@ -279,18 +209,17 @@ static bool capturing(hipStream_t stream) {
 
 // free a slot's buffers (its stream's work, or its graph, is done)
 static void slot_free(WsStreamWs& w) {
-    (void)hipFree(w.ws);
-    (void)hipFree(w.ews);
-    (void)hipFree(w.tws);
-    (void)hipFree(w.pws);
-    (void)hipFree(w.aws);
+    for (auto& b : w.buf) {
+        (void)hipFree(b.p);
+        b = WsBuf{};
+    }
     if (w.hws) (void)hipHostFree(w.hws);
     if (w.adv_h) (void)hipHostFree(w.adv_h);
     for (auto& r : w.retired) (void)hipFree(r.first);
     w.retired.clear();
-    w.ws = nullptr; w.ews = nullptr; w.tws = nullptr; w.pws = nullptr; w.aws = nullptr; w.hws = nullptr; w.hws_dev = nullptr;
+    w.hws = nullptr; w.hws_dev = nullptr;
     w.adv_h = nullptr; w.adv_d = nullptr;
-    w.ws_bytes = w.ews_bytes = w.tws_bytes = w.pws_bytes = w.aws_bytes = w.hws_bytes = 0;
+    w.hws_bytes = 0;
     w.aux_state_ok = false;
     w.aws_gen = 0;
     w.stream = nullptr;
@@ -319,18 +248,19 @@ static bool replays_done(WsStreamWs& w) {
 // zero the resting heads of a slot's buffers (decode/reassembly/stream workspace: 16 B; the
 // auxiliary scratch: WS_AUX_HEAD) outside any capture: private stream, relaxed capture mode
 static int slot_rezero(WsStreamWs& w) {
-    if (!w.ws && !w.aws) return 0;
+    const WsBuf &ws = w.buf[WS_BUF_DECODE], &aws = w.buf[WS_BUF_AUX];
+    if (!ws.p && !aws.p) return 0;
     hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
     (void)hipThreadExchangeStreamCaptureMode(&m);
     hipStream_t ps = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-    if (e == hipSuccess && w.ws) e = hipMemsetAsync(w.ws, 0, 16, ps);
-    if (e == hipSuccess && w.aws) e = hipMemsetAsync(w.aws, 0, w.aws_bytes < WS_AUX_ZERO ? w.aws_bytes : WS_AUX_ZERO, ps);
+    if (e == hipSuccess && ws.p) e = hipMemsetAsync(ws.p, 0, 16, ps);
+    if (e == hipSuccess && aws.p) e = hipMemsetAsync(aws.p, 0, aws.bytes < WS_AUX_ZERO ? aws.bytes : WS_AUX_ZERO, ps);
     if (e == hipSuccess) e = hipStreamSynchronize(ps);
     if (ps) (void)hipStreamDestroy(ps);
     (void)hipThreadExchangeStreamCaptureMode(&m);
     if (e != hipSuccess) return ws_set_err("workspace re-zero (adopted capture slot)", e);
-    if (w.aws) w.aux_state_ok = true;
+    if (aws.p) w.aux_state_ok = true;
     return 0;
 }
 
@@ -396,7 +326,7 @@ static int stream_slot(WsDevState* ds, hipStream_t stream, WsStreamWs** out) {
         if (rc) return rc;
         w = adopt;
         w->dead = 0;
-        if (w->aws) w->aws_gen = ++g_aux_gen;                      // (its plan was zeroed: another call's now)
+        if (w->buf[WS_BUF_AUX].p) w->aws_gen = ++g_aux_gen;                     // (its plan was zeroed: another call's now)
         ++ws_stat_adoptions;
         // the buffers its dead graph's capture replaced: free at the next eager call (not inside a capture)
         ds->deferred.insert(ds->deferred.end(), w->retired.begin(), w->retired.end());
@@ -440,25 +370,23 @@ static int stream_slot(WsDevState* ds, hipStream_t stream, WsStreamWs** out) {
 // grow *p to at least `bytes`. Eagerly: the stream's previous work may still read it, so drain
 // first. While capturing a graph (relaxed-mode allocation), the buffer being replaced stays
 // alive until the slot is released (kernels captured earlier in this graph use it).
-static int grow(WsStreamWs* w, void** p, size_t* have, size_t bytes, hipStream_t stream, size_t zero_bytes,
-                const char* what) {
-    if (*have >= bytes) return 0;
+static int grow(WsStreamWs* w, WsBuf* b, size_t bytes, hipStream_t stream, size_t zero_bytes, const char* what) {
+    if (b->bytes >= bytes) return 0;
     hipError_t e;
     const bool cap = capturing(stream);
-    if (*p) {
+    if (b->p) {
         if (cap) {
-            w->retired.emplace_back(*p, *have);
+            w->retired.emplace_back(b->p, b->bytes);
         } else {
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return ws_set_err("hipStreamSynchronize", e);
-            (void)hipFree(*p);
+            (void)hipFree(b->p);
         }
-        *p = nullptr;
-        *have = 0;
+        *b = WsBuf{};
     }
     const size_t sz = bytes + bytes / 4 + 4096;
     hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
     if (cap) (void)hipThreadExchangeStreamCaptureMode(&mode);
-    e = hipMalloc(p, sz);
+    e = hipMalloc(&b->p, sz);
     if (cap) (void)hipThreadExchangeStreamCaptureMode(&mode);
     if (e != hipSuccess) return ws_set_err(what, e);
     if (zero_bytes && cap) {
@@ -467,15 +395,15 @@ static int grow(WsStreamWs* w, void** p, size_t* have, size_t bytes, hipStream_t
         hipStreamCaptureMode m2 = hipStreamCaptureModeRelaxed;
         (void)hipThreadExchangeStreamCaptureMode(&m2);
         e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, zero_bytes < sz ? zero_bytes : sz, ps);
+        if (e == hipSuccess) e = hipMemsetAsync(b->p, 0, zero_bytes < sz ? zero_bytes : sz, ps);
         if (e == hipSuccess) e = hipStreamSynchronize(ps);
         if (ps) (void)hipStreamDestroy(ps);
         (void)hipThreadExchangeStreamCaptureMode(&m2);
         if (e != hipSuccess) return ws_set_err(what, e);
-    } else if (zero_bytes && (e = hipMemsetAsync(*p, 0, zero_bytes < sz ? zero_bytes : sz, stream)) != hipSuccess) {
+    } else if (zero_bytes && (e = hipMemsetAsync(b->p, 0, zero_bytes < sz ? zero_bytes : sz, stream)) != hipSuccess) {
         return ws_set_err(what, e);
     }
-    *have = sz;
+    b->bytes = sz;
     return 0;
 }
 
@@ -509,37 +437,14 @@ int WsSlot::acquire(hipStream_t stream) {
     return stream_slot(ds, stream, &w);
 }
 
-int WsSlot::workspace(size_t bytes, size_t zero_bytes, void** out) {
+// one of the slot's device buffers, of at least `bytes` (the aux scratch: aux() below)
+int WsSlot::buffer(WsBufKind kind, size_t bytes, size_t zero_bytes, void** out) {
     std::lock_guard<std::mutex> lk(g_dev_mu);
-    void* p = w->ws;
-    const int rc = grow(w, &p, &w->ws_bytes, bytes, st, zero_bytes < 16 ? 16 : zero_bytes, "hipMalloc(workspace)");
-    w->ws = reinterpret_cast<u32*>(p);
+    WsBuf& b = w->buf[kind];
+    if (kind == WS_BUF_DECODE && zero_bytes < 16) zero_bytes = 16;         // its disorder word rests at zero
+    const int rc = grow(w, &b, bytes, st, zero_bytes, g_buf_what[kind]);
     if (rc) return rc;
-    *out = p;
-    return 0;
-}
-
-int WsSlot::encode_workspace(size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    const int rc = grow(w, &w->ews, &w->ews_bytes, bytes, st, 0, "hipMalloc(encode workspace)");
-    if (rc) return rc;
-    *out = w->ews;
-    return 0;
-}
-
-int WsSlot::text_workspace(size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    const int rc = grow(w, &w->tws, &w->tws_bytes, bytes, st, 0, "hipMalloc(text workspace)");
-    if (rc) return rc;
-    *out = w->tws;
-    return 0;
-}
-
-int WsSlot::proto_workspace(size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    const int rc = grow(w, &w->pws, &w->pws_bytes, bytes, st, 0, "hipMalloc(protocol check workspace)");
-    if (rc) return rc;
-    *out = w->pws;
+    *out = b.p;
     return 0;
 }
 
@@ -548,12 +453,11 @@ int WsSlot::proto_workspace(size_t bytes, void** out) {
 // a pinned, device-visible host part grown after draining the stream (never while capturing)
 int WsSlot::aux(size_t dbytes, size_t hbytes, WsAux* out) {
     std::lock_guard<std::mutex> lk(g_dev_mu);
-    const void* before = w->aws;
-    const size_t have = w->aws_bytes;
-    int rc = grow(w, &w->aws, &w->aws_bytes, dbytes < WS_AUX_HEAD ? WS_AUX_HEAD : dbytes, st, WS_AUX_ZERO,
-                  "hipMalloc(aux workspace)");
+    WsBuf& aws = w->buf[WS_BUF_AUX];
+    const WsBuf before = aws;
+    int rc = grow(w, &aws, dbytes < WS_AUX_HEAD ? WS_AUX_HEAD : dbytes, st, WS_AUX_ZERO, g_buf_what[WS_BUF_AUX]);
     if (rc) return rc;
-    if (w->aws != before || w->aws_bytes != have) {                         // freshly zeroed
+    if (aws.p != before.p || aws.bytes != before.bytes) {                   // freshly zeroed
         w->aux_state_ok = true;
         w->aws_gen = ++g_aux_gen;
     }
@@ -573,7 +477,7 @@ int WsSlot::aux(size_t dbytes, size_t hbytes, WsAux* out) {
             return ws_set_err("hipHostGetDevicePointer(aux scratch)", e);
         w->hws_bytes = sz;
     }
-    out->d = w->aws;
+    out->d = aws.p;
     out->h = w->hws;
     out->h_dev = w->hws_dev;
     out->state_ok = &w->aux_state_ok;
@@ -638,8 +542,10 @@ bool ws_capturing(hipStream_t stream) { return capturing(stream); }
 bool ws_aux_alive(const void* base, size_t bytes, unsigned long long gen) {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     for (auto& d : g_dev)
-        for (auto& w : d.sw)
-            if (w.aws && w.aws == base && w.aws_bytes >= bytes && w.aws_gen == gen) return true;
+        for (auto& w : d.sw) {
+            const WsBuf& aws = w.buf[WS_BUF_AUX];
+            if (aws.p && aws.p == base && aws.bytes >= bytes && w.aws_gen == gen) return true;
+        }
     return false;
 }
 
@@ -698,7 +604,7 @@ int ws_decode_range(unsigned char* d_buf, u64 lo, u64 hi, const u64* d_seg_off, 
     // advised that nearly every segment held frames of one length (eager calls only)
     const u32 g0 = adv_h && __atomic_load_n(adv_h, __ATOMIC_RELAXED) == 1 ? (u32)__atomic_load_n(adv_h + 1, __ATOMIC_RELAXED)
                                                                          : 0u;
-    if (!ws && need && (rc = slot.workspace(need, 16, &ws))) return rc;
+    if (!ws && need && (rc = slot.buffer(WS_BUF_DECODE, need, 16, &ws))) return rc;
     const u32* disorder = nullptr;
     bool fallback = false;
     if ((rc = ws_launch_piece(L, lo, hi, reinterpret_cast<unsigned char*>(ws), gen, adv_d, &disorder, &fallback,

@@ -266,6 +266,17 @@ __device__ __forceinline__ bool ws_round_advance(const WsRound& r, u64& off, u64
 // a launch-tuning option (websocketframeGpuSetOption): atomic, so concurrent calls and
 // SetOption never race; each launcher reads the knobs it needs once per call
 typedef std::atomic<int> WsOpt;
+// Every knob and counter, declared once; each is defined, with its measurements, in the file that reads it.
+// ws_api.hip's tables name them and hold the options' ranges: a reader may rely on a knob lying inside its row's.
+extern WsOpt ws_piece_lds, ws_piece_win, ws_seg_win, ws_scan_alpha, ws_k2_timing, ws_reasm_path, ws_reasm_cfg, ws_enc_front;
+extern WsOpt ws_stream_rw, ws_stream_rw_cmax, ws_stream_rounds, ws_stream_plink, ws_stream_win, ws_stream_split_capture,
+    ws_stream_split, ws_stream_split_wait, ws_stream_split2, ws_stream_c0, ws_stream_c1, ws_stream_side_prio;
+extern std::atomic<size_t> ws_host_chunk_bytes;
+extern std::atomic<unsigned long long> ws_stat_rw_chunks, ws_stat_rw_chunk_walks, ws_stat_stream_skips, ws_stat_stream_splits,
+    ws_stat_host_groups, ws_stat_adoptions, ws_stat_adoption_refusals, ws_stat_k2_windows;
+void ws_k2_timing_reset();
+int ws_k2_stat(unsigned long long* ns, unsigned long long* calls);
+size_t ws_workspace_bytes_total();
 int ws_set_err(const char* what, hipError_t e);
 int ws_set_msg(const char* msg);
 
@@ -298,6 +309,8 @@ struct PieceWs {          // ws_piece.hip workspace views after K1
     WsSegRec* segr = nullptr;   // per segment (K1 writes it; the raw-stream path leaves it null)
     u64 npieces, pbase, c_lo, c_hi;
 };
+struct WsPieceLayout;     // (ws_layout.h) -> the views of a workspace at ws
+void ws_piece_views(const WsPieceLayout& Y, unsigned char* ws, PieceWs& P);
 int ws_launch_piece_scan(const WsLaunch& L, u64 lo, u64 hi, unsigned char* ws, u32 gen, PieceWs* out,
                          bool count_nonuniform = false, u32 g0 = 0);
 int ws_launch_piece_unmask(const WsLaunch& L, const PieceWs& P, u32 gen, int* advice = nullptr, u32 g0 = 0);
@@ -322,6 +335,14 @@ struct WsAux {
 // buffer a call needs comes from the one slot it acquired, and LRU eviction never takes a
 // pinned slot. Buffers grow on demand (eagerly: after draining the stream).
 struct WsStreamWs;
+enum WsBufKind {          // a slot's grow-on-demand device buffers
+    WS_BUF_DECODE,        // decode / reassembly / stream workspace (at least its first 16 B zeroed at allocation)
+    WS_BUF_ENCODE,        // scan temp + piece pointers
+    WS_BUF_TEXT,          // the text validator (ws_utf8.hip: per-slot records + tile scan)
+    WS_BUF_PROTO,         // the protocol check (ws_proto.hip: segment offsets + tile summaries)
+    WS_BUF_AUX,           // auxiliary scratch (the stream path's chunk-parallel walk): handed out by aux()
+    WS_BUF_KINDS
+};
 struct WsSlot {
     WsStreamWs* w = nullptr;
     hipStream_t st = nullptr;
@@ -329,10 +350,7 @@ struct WsSlot {
     ~WsSlot();
     int acquire(hipStream_t stream);
     void release();
-    int workspace(size_t bytes, size_t zero_bytes, void** out);   // decode / reassembly / stream
-    int encode_workspace(size_t bytes, void** out);
-    int text_workspace(size_t bytes, void** out);                  // the text validator (ws_utf8.hip)
-    int proto_workspace(size_t bytes, void** out);                 // the protocol check (ws_proto.hip)
+    int buffer(WsBufKind kind, size_t bytes, size_t zero_bytes, void** out);
     int aux(size_t dbytes, size_t hbytes, WsAux* out);
     int advice(int** host, int** dev);                             // the stride hint words (eager)
     int side(hipStream_t* side, hipEvent_t* ev, int prio);         // the raw stream's split walk: side stream + events
@@ -367,4 +385,3 @@ static inline WsWinGrid ws_win_grid(u32 n, int opt) {
     const u32 ppw = wsh ? (u32)(((u64)n + (1u << wsh) - 1) >> wsh) : n;
     return WsWinGrid{wsh, ppw, wsh ? ppw << wsh : n};
 }
-extern WsOpt ws_seg_win;

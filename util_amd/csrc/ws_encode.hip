@@ -549,7 +549,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchEncodeDevice(const unsigned
         // F1 tile sums -> F2 tile scan (also wire_off[n]) -> F3 offsets, piece pointers, edges
         const u32 B = (nframes + ENC_TILE - 1) / ENC_TILE, blocks = B;
         const size_t ptr_off = ((size_t)(B + 1) * 8 + 255) & ~(size_t)255;
-        if ((rc = slot.encode_workspace(ptr_off + npieces * 4 + 16, &ws))) return rc;
+        if ((rc = slot.buffer(WS_BUF_ENCODE, ptr_off + npieces * 4 + 16, 0, &ws))) return rc;
         u64* tpre = reinterpret_cast<u64*>(ws);
         ptr = reinterpret_cast<u32*>(reinterpret_cast<unsigned char*>(ws) + ptr_off);
         hipLaunchKernelGGL(ws_enc_tsum_kernel, dim3(blocks), dim3(ENC_TILE), 0, st, d_frames, nframes, tpre);
@@ -566,7 +566,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeBatchEncodeDevice(const unsigned
         if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, in, d_wire_off, nframes + 1, st)) != hipSuccess)
             return ws_set_err("hipcub scan (size)", e);
         const size_t ptr_off = (scan_bytes + 255) & ~(size_t)255;
-        if ((rc = slot.encode_workspace(ptr_off + npieces * 4 + 16, &ws))) return rc;
+        if ((rc = slot.buffer(WS_BUF_ENCODE, ptr_off + npieces * 4 + 16, 0, &ws))) return rc;
         if ((e = hipcub::DeviceScan::ExclusiveSum(ws, scan_bytes, in, d_wire_off, nframes + 1, st)) != hipSuccess)
             return ws_set_err("hipcub scan", e);
         ptr = reinterpret_cast<u32*>(reinterpret_cast<unsigned char*>(ws) + ptr_off);

@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "ws_layout.h"
 #include "ws_walk.h"
 
 #define PIECE_T 256
@@ -472,21 +473,20 @@ __global__ __launch_bounds__(PIECE_T) void ws_piece_unmask_kernel(unsigned char*
     }
 }
 
-// ws layout: [disorder u32 | nonuni u32 | pad to 16][ptr: npieces u64][nwork: nseg u32][items: nseg*max_frames x 16 B]
+// The workspace's layout: ws_piece_layout (ws_layout.h).
 // No per-call reset: K1 writes every piece pointer, and marks an unordered batch by
 // storing this call's generation number `gen` (never 0) into `disorder`, which the
 // workspace owner zeroes once when it allocates the workspace. `nonuni` (K1's count of
 // segments with frames of several lengths) rests at zero: K2 reads and clears it.
-static u64 piece_count(u64 lo_org, u64 hi_org) {
-    return hi_org > lo_org ? ((hi_org - 1) >> PIECE_SHIFT) - (lo_org >> PIECE_SHIFT) + 1 : 0;
-}
+static_assert(sizeof(WsSegRec) == 16, "ws_layout.h places 16-B segment records");
+size_t ws_piece_workspace_bytes(u64 span, u32 nseg, u32 max_frames) { return ws_piece_bytes(span, nseg, max_frames); }
 
-size_t ws_piece_workspace_bytes(u64 span, u32 nseg, u32 max_frames) {
-    const u64 npieces = (span + 15) / (1ull << PIECE_SHIFT) + 2;
-    size_t b = (16 + npieces * 8 + 15) & ~(size_t)15;
-    b = (b + (size_t)nseg * 4 + 31) & ~(size_t)31;
-    b += (size_t)nseg * sizeof(WsSegRec);
-    return b + (size_t)nseg * max_frames * 16 + 16;
+void ws_piece_views(const WsPieceLayout& Y, unsigned char* ws, PieceWs& P) {
+    P.npieces = Y.npieces; P.pbase = Y.pbase; P.c_lo = Y.c_lo; P.c_hi = Y.c_hi;
+    P.disorder = reinterpret_cast<u32*>(ws + Y.disorder); P.nonuni = reinterpret_cast<u32*>(ws + Y.nonuni);
+    P.ptr = reinterpret_cast<u64*>(ws + Y.ptr); P.nwork = reinterpret_cast<u32*>(ws + Y.nwork);
+    P.segr = Y.segr ? reinterpret_cast<WsSegRec*>(ws + Y.segr) : nullptr;
+    P.items = reinterpret_cast<u32x4*>(ws + Y.items);
 }
 
 // "scan_alpha": 1 (default) the walk switches to alphabet speculation once lengths keep changing,
@@ -498,20 +498,7 @@ WsOpt ws_scan_alpha{1};
 // for the K2 that follows (ws_launch_piece); other users pass false.
 static WalkArgs piece_scan_args(const WsLaunch& L, u64 lo, u64 hi, unsigned char* ws, u32 gen, PieceWs& P, u32 g0) {
     const u64 lead0 = reinterpret_cast<uintptr_t>(L.buf) & 15;
-    const u64 lo_org = lo + lead0, hi_org = hi + lead0;
-    P.npieces = piece_count(lo_org, hi_org);
-    P.pbase = lo_org >> PIECE_SHIFT;
-    P.c_lo = lo_org >> 4;
-    P.c_hi = (hi_org + 15) >> 4;
-    P.disorder = reinterpret_cast<u32*>(ws);
-    P.nonuni = reinterpret_cast<u32*>(ws) + 1;
-    P.ptr = reinterpret_cast<u64*>(ws + 16);
-    size_t b = (16 + P.npieces * 8 + 15) & ~(size_t)15;
-    P.nwork = reinterpret_cast<u32*>(ws + b);
-    b = (b + (size_t)L.nseg * 4 + 31) & ~(size_t)31;
-    P.segr = reinterpret_cast<WsSegRec*>(ws + b);
-    b += (size_t)L.nseg * sizeof(WsSegRec);
-    P.items = reinterpret_cast<u32x4*>(ws + b);
+    ws_piece_views(ws_piece_layout(lo + lead0, hi + lead0, L.nseg, L.max_frames, true), ws, P);
     WalkArgs W;
     W.buf = L.buf; W.seg_off = L.seg_off; W.seg_len = L.seg_len; W.nseg = L.nseg; W.max_frames = L.max_frames;
     W.desc_base = L.desc_base; W.desc = L.desc; W.res = L.res; W.items = P.items; W.ptr = P.ptr; W.nwork = P.nwork;
@@ -590,7 +577,7 @@ WsOpt ws_piece_win{-1};  // "piece_win": log2 of the number of piece windows K2 
 
 int ws_piece_dyn_lds(const WsLaunch& L, u64 npieces, u32 g0) {
     const int opt = ws_piece_lds;
-    if (opt > 0) return opt <= 65536 ? opt : 65536;
+    if (opt > 0) return opt;
     // 7 blocks per CU for frames of <= 16 KiB (several per piece), 6 for larger ones; the frame
     // length is the previous call's advice when it had frames of one length (g0), else the
     // batch's segment density stands in for it

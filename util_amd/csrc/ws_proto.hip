@@ -358,7 +358,7 @@ extern "C" WSFRAME_AMD_PROTO_EXPORT int websocketframeBatchCheckProtocolDevice(
     int rc = slot.acquire(st);
     if (rc) return rc;
     void* p = nullptr;
-    if ((rc = slot.proto_workspace(bytes, &p))) return rc;
+    if ((rc = slot.buffer(WS_BUF_PROTO, bytes, 0, &p))) return rc;
     unsigned char* const ws = reinterpret_cast<unsigned char*>(p);
     u32* const head = reinterpret_cast<u32*>(ws);
     u32* const bo = reinterpret_cast<u32*>(ws + bo_off);

@@ -771,7 +771,7 @@ extern "C" WSFRAME_AMD_CTL_EXPORT int websocketframeBatchReassembleDeviceCtl(
     void* ws = nullptr;
     WsSlot slot;
     int rc = slot.acquire(st);
-    if (rc || (rc = slot.workspace(nb_off + (size_t)nseg * 4 + 64, 16, &ws))) return rc;
+    if (rc || (rc = slot.buffer(WS_BUF_DECODE, nb_off + (size_t)nseg * 4 + 64, 16, &ws))) return rc;
     unsigned char* w8 = reinterpret_cast<unsigned char*>(ws);
     GatherRec* recs = reinterpret_cast<GatherRec*>(w8 + rec_off);
     u32* nbody = reinterpret_cast<u32*>(w8 + nb_off);

@@ -89,6 +89,14 @@ WS_STEP_FN u32 ws_cand_code(u64 pos, u64 limit, u64 index, u32 max_frames, const
 WS_STEP_FN u32 ws_status_bits(int status) { return (u32)status & 3u; }
 WS_STEP_FN int ws_bits_status(u32 bits) { return (int)(bits ^ 2u) - 2; }
 
+// the unmask kernel's unit (ws_piece.hip K2, also behind the raw-stream path): one-shot
+// 256-thread blocks over WS_PIECE_U KiB per wave, 2^WS_PIECE_SHIFT bytes per block
+// (ws_layout.h counts a workspace's pieces by it)
+#ifndef WS_PIECE_U
+#define WS_PIECE_U 4
+#define WS_PIECE_SHIFT 14                   // 16 KiB = 256 threads * WS_PIECE_U * 16 B
+#endif
+
 #ifdef __HIPCC__
 // ---------------------------------------------------------------------------------------------
 // Device part.
@@ -108,13 +116,6 @@ template <typename T>
 __device__ __forceinline__ WS_GLOBAL T* gptr(const void* p) {
     return reinterpret_cast<WS_GLOBAL T*>(reinterpret_cast<uintptr_t>(p));
 }
-
-// the unmask kernel's unit (ws_piece.hip K2, also behind the raw-stream path): one-shot
-// 256-thread blocks over WS_PIECE_U KiB per wave, 2^WS_PIECE_SHIFT bytes per block
-#ifndef WS_PIECE_U
-#define WS_PIECE_U 4
-#define WS_PIECE_SHIFT 14                   // 16 KiB = 256 threads * WS_PIECE_U * 16 B
-#endif
 
 __device__ __forceinline__ u32 rotl32(u32 x, u32 r) { return r ? (x << r) | (x >> (32 - r)) : x; }
 

@@ -24,7 +24,7 @@
 
 #include "ws_common.h"
 #include "ws_link.h"
-#include "ws_rwplan.h"
+#include "ws_layout.h"
 
 #define SPASS_T 256
 
@@ -1203,35 +1203,74 @@ int ws_stream_plan_stat(const char* name, unsigned long long* value) {
 
 // scratch for the chunk-parallel walk: the call's slot's auxiliary workspace (device
 // records + counters, and a pinned host copy of them), so concurrent calls on different
-// streams never share it (the walk runs in eager calls only)
-struct RwScratch {
-    void* d = nullptr;
-    void* h = nullptr;
-};
-
-// (the aux head holds the pass loop's state and the 256 B after it the device walk's plan,
-// RwPlan: the host-linked walk's device scratch starts after both, so a slot that serves both
-// kinds of call never hands the plan this walk's leftovers — ADVICE r05)
-static int rw_scratch(WsSlot& slot, size_t dbytes, size_t hbytes, RwScratch* out) {
-    WsAux A;
-    const int rc = slot.aux(WS_AUX_ZERO + dbytes, WS_AUX_HEAD + hbytes, &A);
+// streams never share it (the walk runs in eager calls only). The aux head holds the pass loop's
+// state and the 256 B after it the device walk's plan, RwPlan: the host-linked walk's device
+// scratch starts after both, so a slot that serves both kinds of call never hands the plan this
+// walk's leftovers.
+static int rw_scratch(WsSlot& slot, size_t dbytes, size_t hbytes, WsAux* S) {
+    const int rc = slot.aux(WS_AUX_ZERO + dbytes, WS_AUX_HEAD + hbytes, S);
     if (rc) return rc;
-    out->d = reinterpret_cast<unsigned char*>(A.d) + WS_AUX_ZERO;
-    out->h = reinterpret_cast<unsigned char*>(A.h) + WS_AUX_HEAD;
+    S->d = reinterpret_cast<unsigned char*>(S->d) + WS_AUX_ZERO;
+    S->h = reinterpret_cast<unsigned char*>(S->h) + WS_AUX_HEAD;
     return 0;
 }
 
+// a region of the chunk-walk scratch (RwLayout, ws_layout.h) at `base`
+template <class T>
+static T* rw_at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<unsigned char*>(base) + off); }
+
+// The split of a device-planned walk (round 6, VERDICT r05 item 3): K2 runs as one launch per
+// part (pieces [0, p[0]), [p[0], p[1]), ..., [p[last], npieces)), and the walk of each part after
+// part 0 runs on a side stream while the earlier launches stream. Side-stream work joins the
+// caller's stream through events (a capture forks and joins through them too: the side stream's
+// work becomes a graph branch, option stream_split_capture).
+struct RwSplit {
+    u32 ncut = 0;                // K2 cut points (parts - 1); 0 = no split
+    u64 p[RW_NP - 1] = {};       // the cuts (pieces)
+    u64 x[RW_NP - 1] = {};       // the first stream byte of the piece at each cut
+    hipStream_t side = nullptr;
+    hipEvent_t ev[RW_NP + 1] = {};   // side start, part 0 done, part 1 done, ...
+    int wait = 0;                // part 1's R1-R3 start after: 0 the plan, 1 part 0's R3, 2 part 0's emit
+    u32 shift[RW_NP - 1] = {2, 1};   // part 0's / a middle part's chunks: C >> shift
+};
+
+// where the plan kernel of a device-planned walk starts (its `fresh` argument)
+enum RwStart {
+    RW_START_AT_STATE = 0,       // where the pass rounds stopped (sd->P; nothing to do if they finished)
+    RW_START_AT_ZERO = 1,        // no pass rounds ran: the previous walk on this stream hinted at changing lengths
+    RW_START_BY_DEVICE_HINT = 2  // captured: the rounds were enqueued, the previous replay's hint says whether they ran
+};
+
+// One raw-stream call: what its helpers share (websocketframeStreamDecodeDevice builds it once)
+struct RwCall {
+    WsSlot& slot;
+    unsigned char* d_buf; u64 len; u32 max_frames;
+    WebsocketFrameDesc_t* d_desc; WebsocketSegResult_t* d_res; hipStream_t st;
+    WsLaunch L;                  // the same, as K2's launcher takes them
+    u32 gen;                     // the call's generation number (K2)
+    PieceWs Pw;
+    u64* d_seg;                  // the one segment's (offset, length) pair
+    SdState* sd;                 // the pass loop's state (aux head)
+    bool* state_ok;              // ... rests where the next call expects it
+    unsigned char* w;            // the device-planned walk's scratch (after the aux head) and its layout
+    RwDevLayout RL;
+    unsigned long long aux_gen;
+    RwSplit sp;
+    int walk(u64 P, u32 nf) const;                                   // host-linked
+    int walk_device(RwStart start, SdMirror* mirror) const;
+    int unmask() const;                                              // K2 after a device-planned walk
+    int walk_device_unmask(RwStart start, SdMirror* mirror) const;
+};
 
 // The chunk-parallel walk of [P, len) with nf frames before P (see above). Launches the
 // emit kernels and, for chunks without a link, one-wavefront chunk walks; the last of
 // them writes the tail pointers, item count and segment result.
-static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u32 max_frames,
-                   WebsocketFrameDesc_t* d_desc, const PieceWs& Pw, WebsocketSegResult_t* d_res, hipStream_t st) {
+int RwCall::walk(u64 P, u32 nf) const {
     hipError_t e;
     int rc;
     ws_stat_rw_chunk_walks = 0;
     ws_stat_rw_chunks = 0;
-    RwScratch S;
+    WsAux S;
     u64* wout = nullptr;       // chunk-walk report (device) and its pinned copy
     u64* ho = nullptr;
     // one chunk [ent, end) by one wavefront: the next entry, or the stream finished
@@ -1276,41 +1315,28 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
         if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_stream_walk_kernel launch", e);
         return 0;
     }
-    const int cmax_log = ws_stream_rw_cmax;                                  // one read per call
-    const u64 cmax = cmax_log >= 16 && cmax_log <= 26 ? 1ull << cmax_log : RW_CMAX;
-    const RwHostGeom HG = rw_host_geometry(P, len, mean, cmax);              // (ws_rwplan.h)
+    const RwHostGeom HG = rw_host_geometry(P, len, mean, 1ull << ws_stream_rw_cmax);   // (ws_rwplan.h; one read per call)
     const u64 C = HG.C, nchunks = HG.nchunks;
     const u32 H = HG.H, stgn = HG.stgn, capc = HG.capc;
-    const size_t b_recs = ((size_t)(nchunks * RW_SLOTS + RW_SLAST) * sizeof(RwRec) + 255) & ~(size_t)255;
-    const size_t b_nrec = ((size_t)nchunks * 16 + 255) & ~(size_t)255;     // per chunk: n0, n1, candidates
-    const size_t b_dx = ((size_t)nchunks * RW_D * 8 + 255) & ~(size_t)255;
-    const size_t b_own = ((size_t)nchunks * RW_D * sizeof(RwOwn) + 255) & ~(size_t)255;
-    const size_t b_tab = ((size_t)nchunks * sizeof(RwRow) + 255) & ~(size_t)255;
     // staging: about twice the chunk's mean frame count (frames past it are walked by the emit)
-    const size_t b_stg = (size_t)nchunks * RW_D * stgn * 4;
-    const size_t b_cand = (size_t)nchunks * capc * 8;
-    const size_t b_host = b_recs + b_nrec + b_dx + 256 + b_own;              // copied back
-    if ((rc = rw_scratch(slot, 256 + b_host + b_tab + b_stg + b_cand, 256 + b_host, &S))) return rc;
-    unsigned char* w = reinterpret_cast<unsigned char*>(S.d);
-    unsigned char* hw = reinterpret_cast<unsigned char*>(S.h);
-    wout = reinterpret_cast<u64*>(w);
-    ho = reinterpret_cast<u64*>(hw);
-    RwRec* recs = reinterpret_cast<RwRec*>(w + 256);
-    u32* nrec = reinterpret_cast<u32*>(w + 256 + b_recs);
-    unsigned long long* dx = reinterpret_cast<unsigned long long*>(w + 256 + b_recs + b_nrec);
-    RwOwn* own = reinterpret_cast<RwOwn*>(w + 256 + b_recs + b_nrec + b_dx + 256);
-    RwRow* tab = reinterpret_cast<RwRow*>(w + 256 + b_host);
-    u32* stg = reinterpret_cast<u32*>(w + 256 + b_host + b_tab);
-    u64* cand = reinterpret_cast<u64*>(w + 256 + b_host + b_tab + b_stg);
-    const RwRec* hr = reinterpret_cast<const RwRec*>(hw + 256);
-    const u32* hn = reinterpret_cast<const u32*>(hw + 256 + b_recs);
-    const u64* hdx = reinterpret_cast<const u64*>(hw + 256 + b_recs + b_nrec);
-    const RwOwn* hown = reinterpret_cast<const RwOwn*>(hw + 256 + b_recs + b_nrec + b_dx + 256);
+    const RwLayout Y = rw_carve(nchunks, nchunks * RW_D * stgn, nchunks * capc, 0, 0);
+    // (the pinned copy: the chunk report, then the counters, exits, records and owners copied back)
+    if ((rc = rw_scratch(slot, Y.bytes, Y.o_tab, &S))) return rc;
+    wout = rw_at<u64>(S.d, Y.o_plan);
+    ho = rw_at<u64>(S.h, Y.o_plan);
+    // (device, pinned copy) per chunk: n0, n1, candidates; the claimed exits; the records; the owner walks
+    u32 *nrec = rw_at<u32>(S.d, Y.o_nrec), *hn = rw_at<u32>(S.h, Y.o_nrec);
+    unsigned long long *dx = rw_at<unsigned long long>(S.d, Y.o_dx), *hdx = rw_at<unsigned long long>(S.h, Y.o_dx);
+    RwRec *recs = rw_at<RwRec>(S.d, Y.o_recs), *hr = rw_at<RwRec>(S.h, Y.o_recs);
+    RwOwn *own = rw_at<RwOwn>(S.d, Y.o_own), *hown = rw_at<RwOwn>(S.h, Y.o_own);
+    RwRow* tab = rw_at<RwRow>(S.d, Y.o_tab);
+    u32* stg = rw_at<u32>(S.d, Y.o_stg);
+    u64* cand = rw_at<u64>(S.d, Y.o_cand);
     // the stream's frames are masked if the one at P is (client streams): candidates must be too
     unsigned char* hb = reinterpret_cast<unsigned char*>(ho + 4);
     hb[1] = 0;
     if ((e = hipMemcpyAsync(hb, d_buf + P, 2, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipMemsetAsync(nrec, 0, b_nrec + b_dx + 256, st)) != hipSuccess ||  // counters, claimed exits
+        (e = hipMemsetAsync(nrec, 0, Y.zero_bytes, st)) != hipSuccess ||     // counters, claimed exits
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return ws_set_err("stream walk setup", e);
     const u32 need_mask = (hb[1] & 0x80u) ? 1u : 0u;
@@ -1328,7 +1354,7 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((nchunks * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0, st,
                        d_buf, len, G, dx, own, stg, (const RwPlan*)nullptr, 0);
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_rw_own_kernel launch", e);
-    if ((e = hipMemcpyAsync(hw + 256, w + 256, b_host, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(rw_at<void>(S.h, Y.o_nrec), nrec, Y.back_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return ws_set_err("stream walk records", e);
     // follow the chain from P: exact, every record is the reference loop from its start
@@ -1389,76 +1415,40 @@ static int rw_walk(WsSlot& slot, unsigned char* d_buf, u64 len, u64 P, u32 nf, u
     return 0;
 }
 
-// A captured call's chunk-parallel walk: scratch sized from the stream length (caps), the
-// geometry chosen on the device (ws_rw_plan_kernel). Layout after the aux head.
-struct RwDevLayout {
-    u64 cmin, nch_cap, cand_cap, stg_cap;
-    size_t o_plan, o_recs, o_nrec, o_dx, o_own, o_tab, o_stg, o_cand, o_lk, bytes, zero_bytes;
-};
-static RwDevLayout rw_dev_layout(u64 len) {
-    RwDevLayout L;
-    L.cmin = RW_CMIN;
-    while ((len + L.cmin - 1) / L.cmin + 2 > RW_CAP_CHUNKS) L.cmin <<= 1;
-    L.nch_cap = (len + L.cmin - 1) / L.cmin + 2;
-    L.cand_cap = std::min<u64>(L.nch_cap * (RW_HMAX / 32), len / 1024 + 65536);
-    L.stg_cap = std::min<u64>(L.nch_cap * RW_D * RW_CAP_STGN, len / 256 + 65536);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o = 0;
-    L.o_plan = o; o += up(sizeof(RwPlan));
-    L.o_nrec = o; o += up(L.nch_cap * 16);                                   // zeroed: counters,
-    L.o_dx = o; o += up(L.nch_cap * RW_D * 8);                               // claimed exits
-    L.zero_bytes = o - L.o_nrec;
-    L.o_recs = o; o += up((L.nch_cap * RW_SLOTS + RW_SLAST) * sizeof(RwRec));
-    L.o_own = o; o += up(L.nch_cap * RW_D * sizeof(RwOwn));
-    L.o_tab = o; o += up((L.nch_cap + 2) * sizeof(RwRow));
-    L.o_stg = o; o += up(L.stg_cap * 4);
-    L.o_cand = o; o += up(L.cand_cap * 8);
-    L.o_lk = o; o += up(L.nch_cap * sizeof(RwLink));
-    L.bytes = o;
-    return L;
+// `to` goes on after everything `from` holds so far
+static int rw_fork(hipStream_t from, hipStream_t to, hipEvent_t ev) {
+    hipError_t e = hipEventRecord(ev, from);
+    if (e != hipSuccess) return ws_set_err("hipEventRecord(stream split)", e);
+    if ((e = hipStreamWaitEvent(to, ev, 0)) != hipSuccess) return ws_set_err("hipStreamWaitEvent(stream split)", e);
+    return 0;
 }
 
-// The split of a device-planned walk (round 6, VERDICT r05 item 3): K2 runs as one launch per
-// part (pieces [0, p[0]), [p[0], p[1]), ..., [p[last], npieces)), and the walk of each part after
-// part 0 runs on a side stream while the earlier launches stream. Side-stream work joins the
-// caller's stream through events (a capture forks and joins through them too: the side stream's
-// work becomes a graph branch, option stream_split_capture).
-struct RwSplit {
-    u32 ncut = 0;                // K2 cut points (parts - 1); 0 = no split
-    u64 p[RW_NP - 1] = {};       // the cuts (pieces)
-    u64 x[RW_NP - 1] = {};       // the first stream byte of the piece at each cut
-    hipStream_t side = nullptr;
-    hipEvent_t ev[RW_NP + 1] = {};   // side start, part 0 done, part 1 done, ...
-    int wait = 0;                // part 1's R1-R3 start after: 0 the plan, 1 part 0's R3, 2 part 0's emit
-    u32 shift[RW_NP - 1] = {2, 1};   // part 0's / a middle part's chunks: C >> shift
-};
-
-static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, WebsocketFrameDesc_t* d_desc,
-                          const PieceWs& Pw, WebsocketSegResult_t* d_res, hipStream_t st, SdState* sd,
-                          unsigned char* w, const RwDevLayout& L, unsigned long long aux_gen, int fresh = 0, u64* d_seg = nullptr,
-                          SdMirror* mirror = nullptr, const RwSplit* sp = nullptr) {
-    RwPlan* plan = reinterpret_cast<RwPlan*>(w + L.o_plan);
-    rw_note_device_plan(w - WS_AUX_HEAD, aux_gen, plan);                     // (host words only: the plan stats)
-    u32* nrec = reinterpret_cast<u32*>(w + L.o_nrec);
-    unsigned long long* dx = reinterpret_cast<unsigned long long*>(w + L.o_dx);
-    RwRec* recs = reinterpret_cast<RwRec*>(w + L.o_recs);
-    RwOwn* own = reinterpret_cast<RwOwn*>(w + L.o_own);
-    RwRow* tab = reinterpret_cast<RwRow*>(w + L.o_tab);
-    u32* stg = reinterpret_cast<u32*>(w + L.o_stg);
-    u64* cand = reinterpret_cast<u64*>(w + L.o_cand);
-    RwLink* lk = reinterpret_cast<RwLink*>(w + L.o_lk);
-    const int cmax_log = ws_stream_rw_cmax;                                  // one read per call
-    const bool split = sp && sp->ncut;
+// A device-planned chunk-parallel walk (captured calls; eager ones once lengths keep changing): scratch
+// sized from the stream length (rw_dev_layout's caps), the geometry chosen on the device
+// (ws_rw_plan_kernel). mirror: the pinned state the plan kernel tells the next eager call through.
+int RwCall::walk_device(RwStart start, SdMirror* mirror) const {
+    const RwLayout& Y = RL.at;
+    const u64 nch_cap = RL.nch_cap;
+    RwPlan* plan = rw_at<RwPlan>(w, Y.o_plan);
+    rw_note_device_plan(w - WS_AUX_HEAD, aux_gen, plan);                // (host words only: the plan stats)
+    u32* nrec = rw_at<u32>(w, Y.o_nrec);
+    unsigned long long* dx = rw_at<unsigned long long>(w, Y.o_dx);
+    RwRec* recs = rw_at<RwRec>(w, Y.o_recs);
+    RwOwn* own = rw_at<RwOwn>(w, Y.o_own);
+    RwRow* tab = rw_at<RwRow>(w, Y.o_tab);
+    u32* stg = rw_at<u32>(w, Y.o_stg);
+    u64* cand = rw_at<u64>(w, Y.o_cand);
+    RwLink* lk = rw_at<RwLink>(w, Y.o_lk);
+    const bool split = sp.ncut != 0;
     // a split walk's last part runs beside K2: chunks twice the usual largest (fewer windows for R1 to
     // scan beside the stream; its longer owner walks are hidden), the earlier parts' that >> shift
-    const u64 cmax = std::min<u64>((cmax_log >= 16 && cmax_log <= 26 ? 1ull << cmax_log : RW_CMAX) << (split ? 1 : 0),
-                                   RW_CMAX);
-    hipError_t e = hipMemsetAsync(nrec, 0, L.zero_bytes, st);
+    const u64 cmax = std::min<u64>((1ull << ws_stream_rw_cmax) << (split ? 1 : 0), RW_CMAX);   // (one read per call)
+    hipError_t e = hipMemsetAsync(nrec, 0, Y.zero_bytes, st);
     if (e != hipSuccess) return ws_set_err("hipMemsetAsync(stream walk counters)", e);
-    hipLaunchKernelGGL(ws_rw_plan_kernel, dim3(1), dim3(64), 0, st, d_buf, len, max_frames, sd, plan, L.cmin, cmax,
-                       (u32)L.nch_cap, L.cand_cap, L.stg_cap, d_desc, Pw.items, Pw.ptr, Pw.npieces, Pw.nwork, d_res,
-                       fresh, d_seg, Pw.disorder, mirror, split ? sp->x[0] : 0ull, split && sp->ncut > 1 ? sp->x[1] : 0ull,
-                       split ? sp->shift[0] : 0u, split ? sp->shift[1] : 0u);
+    hipLaunchKernelGGL(ws_rw_plan_kernel, dim3(1), dim3(64), 0, st, d_buf, len, max_frames, sd, plan, RL.cmin, cmax,
+                       (u32)nch_cap, RL.cand_cap, RL.stg_cap, d_desc, Pw.items, Pw.ptr, Pw.npieces, Pw.nwork, d_res,
+                       (int)start, d_seg, Pw.disorder, mirror, split ? sp.x[0] : 0ull,
+                       split && sp.ncut > 1 ? sp.x[1] : 0ull, split ? sp.shift[0] : 0u, split ? sp.shift[1] : 0u);
     // one part's candidate, window and owner walks; its linking and emit
     auto rwalk = [&](hipStream_t s, int part) {
         // R1 and R2 grid-stride, R3 one lane per (chunk, exit): grids for the caps
@@ -1466,12 +1456,12 @@ static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, Websock
                            (const RwPlan*)plan, part);
         hipLaunchKernelGGL(ws_rw_spec_kernel, dim3(RW_R2_GRID), dim3(256), 0, s, d_buf, len, RwGeo{}, (const u64*)cand,
                            recs, nrec, dx, (const RwPlan*)plan, part);
-        hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((L.nch_cap * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0,
+        hipLaunchKernelGGL(ws_rw_own_kernel, dim3((u32)((nch_cap * RW_D + RW_OWN_T - 1) / RW_OWN_T)), dim3(RW_OWN_T), 0,
                            s, d_buf, len, RwGeo{}, (const unsigned long long*)dx, own, stg, (const RwPlan*)plan, part);
     };
     auto rlink = [&](hipStream_t s, int part) {
         if (ws_stream_plink) {      // the chunk-parallel linker; the serial one below exits if it linked
-            hipLaunchKernelGGL(ws_rw_plink_kernel, dim3((u32)L.nch_cap), dim3(64), 0, s, len, (const RwPlan*)plan,
+            hipLaunchKernelGGL(ws_rw_plink_kernel, dim3((u32)nch_cap), dim3(64), 0, s, len, (const RwPlan*)plan,
                                (const RwRec*)recs, (const u32*)nrec, (const unsigned long long*)dx, (const RwOwn*)own,
                                lk, part);
             hipLaunchKernelGGL(ws_rw_pscan_kernel, dim3(1), dim3(RW_PS_T), 0, s, len, max_frames, plan, (const RwLink*)lk, tab,
@@ -1480,40 +1470,32 @@ static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, Websock
         hipLaunchKernelGGL(ws_rw_link_kernel, dim3(1), dim3(64), 0, s, d_buf, len, max_frames, plan, (const RwRec*)recs,
                            (const u32*)nrec, (const unsigned long long*)dx, (const RwOwn*)own, tab, d_desc, Pw.items,
                            Pw.ptr, Pw.npieces, Pw.nwork, d_res, part);
-        hipLaunchKernelGGL(ws_rw_emit_kernel, dim3((u32)(L.nch_cap + 2)), dim3(64), 0, s, d_buf, len, max_frames,
+        hipLaunchKernelGGL(ws_rw_emit_kernel, dim3((u32)(nch_cap + 2)), dim3(64), 0, s, d_buf, len, max_frames,
                            (const RwRow*)tab, (const RwOwn*)own, (const u32*)stg, 0u, d_desc, Pw.items, Pw.ptr,
                            Pw.npieces, Pw.nwork, d_res, plan, part);
     };
     if (!split) {
         rwalk(st, 0);
         rlink(st, 0);
-        if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("stream walk (device) launch", e);
-        return 0;
+    } else {
+        int rc;
+        auto side_part1 = [&]() {                                            // part 1's walks, beside what follows on st
+            const int r = rw_fork(st, sp.side, sp.ev[0]);
+            if (!r) rwalk(sp.side, 1);
+            return r;
+        };
+        if (sp.wait == 0 && (rc = side_part1())) return rc;
+        rwalk(st, 0);
+        if (sp.wait == 1 && (rc = side_part1())) return rc;
+        rlink(st, 0);
+        if ((rc = rw_fork(st, sp.side, sp.ev[1]))) return rc;
+        if (sp.wait >= 2) rwalk(sp.side, 1);
+        for (u32 k = 1; k <= sp.ncut; ++k) {                                 // the parts past part 0, one after the other
+            if (k >= 2) rwalk(sp.side, (int)k);
+            rlink(sp.side, (int)k);
+            if ((e = hipEventRecord(sp.ev[k + 1], sp.side)) != hipSuccess) return ws_set_err("hipEventRecord(stream split)", e);
+        }
     }
-#define RW_TRY(call, what) do { if ((e = (call)) != hipSuccess) return ws_set_err(what, e); } while (0)
-    if (sp->wait == 0) {
-        RW_TRY(hipEventRecord(sp->ev[0], st), "hipEventRecord(stream split)");
-        RW_TRY(hipStreamWaitEvent(sp->side, sp->ev[0], 0), "hipStreamWaitEvent(stream split)");
-        rwalk(sp->side, 1);
-    }
-    rwalk(st, 0);
-    if (sp->wait == 1) {
-        RW_TRY(hipEventRecord(sp->ev[0], st), "hipEventRecord(stream split)");
-        RW_TRY(hipStreamWaitEvent(sp->side, sp->ev[0], 0), "hipStreamWaitEvent(stream split)");
-        rwalk(sp->side, 1);
-    }
-    rlink(st, 0);
-    RW_TRY(hipEventRecord(sp->ev[1], st), "hipEventRecord(stream split)");
-    RW_TRY(hipStreamWaitEvent(sp->side, sp->ev[1], 0), "hipStreamWaitEvent(stream split)");
-    if (sp->wait >= 2) rwalk(sp->side, 1);
-    rlink(sp->side, 1);
-    RW_TRY(hipEventRecord(sp->ev[2], sp->side), "hipEventRecord(stream split)");
-    for (u32 k = 2; k <= sp->ncut; ++k) {                                    // later parts, one after the other
-        rwalk(sp->side, (int)k);
-        rlink(sp->side, (int)k);
-        RW_TRY(hipEventRecord(sp->ev[k + 1], sp->side), "hipEventRecord(stream split)");
-    }
-#undef RW_TRY
     if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("stream walk (device) launch", e);
     return 0;
 }
@@ -1522,14 +1504,14 @@ static int rw_walk_device(unsigned char* d_buf, u64 len, u32 max_frames, Websock
 // (pieces [p[k-1], p[k])) with the item count part k left in the plan, once part k is emitted; the
 // last launch with the stream's final count
 std::atomic<unsigned long long> ws_stat_stream_splits{0};   // raw-stream calls whose K2 ran split (since load)
-static int rw_unmask(const WsLaunch& L, const PieceWs& Pw, u32 gen, const RwSplit* sp, const RwPlan* plan) {
-    if (!sp || !sp->ncut) return ws_launch_piece_unmask(L, Pw, gen);
+int RwCall::unmask() const {
+    if (!sp.ncut) return ws_launch_piece_unmask(L, Pw, gen);
     ++ws_stat_stream_splits;
     const u64 cpp = 1ull << (WS_PIECE_SHIFT - 4);                             // 16-B chunks per piece
-    for (u32 k = 0; k <= sp->ncut; ++k) {
-        const u64 a = k ? sp->p[k - 1] : 0, b = k < sp->ncut ? sp->p[k] : Pw.npieces;
+    for (u32 k = 0; k <= sp.ncut; ++k) {
+        const u64 a = k ? sp.p[k - 1] : 0, b = k < sp.ncut ? sp.p[k] : Pw.npieces;
         if (k) {
-            hipError_t e = hipStreamWaitEvent(L.stream, sp->ev[k + 1], 0);
+            hipError_t e = hipStreamWaitEvent(L.stream, sp.ev[k + 1], 0);
             if (e != hipSuccess) return ws_set_err("hipStreamWaitEvent(stream split join)", e);
         }
         if (b <= a) continue;
@@ -1538,12 +1520,21 @@ static int rw_unmask(const WsLaunch& L, const PieceWs& Pw, u32 gen, const RwSpli
         A.pbase = Pw.pbase + a;
         A.npieces = b - a;
         A.c_lo = std::max<u64>(Pw.c_lo, a * cpp);
-        A.c_hi = k < sp->ncut ? std::min<u64>(Pw.c_hi, b * cpp) : Pw.c_hi;
-        if (k < sp->ncut) A.nwork = const_cast<u32*>(&plan->nw[k]);
+        A.c_hi = k < sp.ncut ? std::min<u64>(Pw.c_hi, b * cpp) : Pw.c_hi;
+        if (k < sp.ncut) A.nwork = &rw_at<RwPlan>(w, RL.at.o_plan)->nw[k];
         const int rc = ws_launch_piece_unmask(L, A, gen);
         if (rc) return rc;
     }
     return 0;
+}
+
+// the device walks the rest, K2 follows (the state rests once the walk is enqueued: a captured call
+// says so here, an eager one has said so already)
+int RwCall::walk_device_unmask(RwStart start, SdMirror* mirror) const {
+    const int rc = walk_device(start, mirror);
+    if (rc) return rc;
+    *state_ok = true;
+    return unmask();
 }
 
 extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char* d_buf, unsigned long long len,
@@ -1556,15 +1547,16 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     hipError_t e;
     // workspace: the piece path's layout for one segment [0, len), then the segment's
-    // (offset, length) pair for the unmask kernel; the pass loop's state rests in the head
-    // of the stream's auxiliary workspace
-    const size_t pws = ws_piece_workspace_bytes(len, 1, max_frames);
+    // (offset, length) pair for the unmask kernel (ws_stream_layout); the pass loop's state rests
+    // in the head of the stream's auxiliary workspace
+    const u64 lead0 = reinterpret_cast<uintptr_t>(d_buf) & 15;
+    const WsStreamLayout WL = ws_stream_layout(lead0, len, max_frames);
     void* ws = nullptr;
     WsSlot slot;                              // every buffer of this call comes from one pinned slot
     int rc = slot.acquire(st);
-    if (rc || (rc = slot.workspace(pws + 64, 16, &ws))) return rc;
+    if (rc || (rc = slot.buffer(WS_BUF_DECODE, WL.bytes, 16, &ws))) return rc;
     unsigned char* w8 = reinterpret_cast<unsigned char*>(ws);
-    u64* d_seg = reinterpret_cast<u64*>(w8 + ((pws + 15) & ~(size_t)15));    // [0] offset 0, [1] length
+    u64* d_seg = reinterpret_cast<u64*>(w8 + WL.seg);                        // [0] offset 0, [1] length
     const bool capture = ws_capturing(st);
     // An eager call on a stream long enough for the chunk-parallel walk reads the state after
     // every round (published by the resolve kernel into pinned host memory, no copy): another
@@ -1580,9 +1572,9 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     // stream_rw 2 asks for the host to follow the chunk records (round 2's eager form)
     const bool dev_rw = rw && len >= RW_MIN && capture;
     const bool dev_layout = rw && len >= RW_MIN && (capture || rw_opt == 1);
-    const RwDevLayout RL = dev_layout ? rw_dev_layout(len) : RwDevLayout{};
+    const RwDevLayout RL = dev_layout ? rw_dev_layout(len, sizeof(RwPlan), sizeof(RwLink)) : RwDevLayout{};
     WsAux A;
-    if ((rc = slot.aux(WS_AUX_HEAD + (dev_layout ? RL.bytes : 0), host_rw ? WS_AUX_HEAD : 0, &A))) return rc;
+    if ((rc = slot.aux(WS_AUX_HEAD + RL.at.bytes, host_rw ? WS_AUX_HEAD : 0, &A))) return rc;
     SdState* sd = reinterpret_cast<SdState*>(A.d);
     SdMirror* hm = host_rw ? reinterpret_cast<SdMirror*>(A.h) : nullptr;
     SdMirror* dm = host_rw ? reinterpret_cast<SdMirror*>(A.h_dev) : nullptr;
@@ -1592,22 +1584,8 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     L.cus = slot.cus; L.lds_per_cu = slot.lds;
     L.pwin = ws_stream_win;
     PieceWs Pw;
+    ws_piece_views(WL.piece, w8, Pw);
     const u32 gen = ws_next_gen();
-    // the piece-path views of the workspace
-    {
-        const u64 lead0 = reinterpret_cast<uintptr_t>(d_buf) & 15;
-        Pw.npieces = len + lead0 ? ((len + lead0 - 1) >> WS_PIECE_SHIFT) + 1 : 0;
-        Pw.pbase = 0;
-        Pw.c_lo = 0;
-        Pw.c_hi = (len + lead0 + 15) >> 4;
-        Pw.disorder = reinterpret_cast<u32*>(w8);
-        Pw.nonuni = reinterpret_cast<u32*>(w8) + 1;
-        Pw.ptr = reinterpret_cast<u64*>(w8 + 16);
-        size_t b = (16 + Pw.npieces * 8 + 15) & ~(size_t)15;
-        Pw.nwork = reinterpret_cast<u32*>(w8 + b);
-        b = (b + 4 + 15) & ~(size_t)15;
-        Pw.items = reinterpret_cast<u32x4*>(w8 + b);
-    }
     if (!*A.state_ok) {                       // a previous call stopped between its launches
         hipLaunchKernelGGL(ws_stream_init_kernel, dim3(1), dim3(1), 0, st, sd);
         if ((e = hipGetLastError()) != hipSuccess) return ws_set_err("ws_stream_init_kernel launch", e);
@@ -1631,39 +1609,34 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
         const hipError_t e2 = hipGetLastError();
         return e2 == hipSuccess ? 0 : ws_set_err("ws_stream_pass_kernel launch", e2);
     };
-    const int nr0 = ws_stream_rounds, nr = nr0 >= 1 && nr0 <= 64 ? nr0 : 4;
+    const int nr = ws_stream_rounds;                                         // one read per call
     // the split of a device-planned walk (RwSplit): K2's first launch owns pieces [0, p0)
     RwSplit SP;
-    unsigned char* const rw_w = reinterpret_cast<unsigned char*>(A.d) + WS_AUX_HEAD;
-    const RwPlan* const rw_plan = reinterpret_cast<const RwPlan*>(rw_w + RL.o_plan);
     // (captured calls too unless stream_split_capture is 0: the side stream's work becomes a graph
     // branch, which the runtime runs beside the unmask's launches)
     if (dev_layout && (!capture || ws_stream_split_capture)) {
-        const int spl = ws_stream_split, spl2 = ws_stream_split2, sw = ws_stream_split_wait;   // one read each
-        const int c0 = ws_stream_c0, c1 = ws_stream_c1, pr = ws_stream_side_prio;
-        if (spl > 0 && spl < 256 && Pw.npieces >= 3) {
-            const u64 lead0 = reinterpret_cast<uintptr_t>(d_buf) & 15;
+        const int spl = ws_stream_split, spl2 = ws_stream_split2;            // one read each
+        if (spl > 0 && Pw.npieces >= 3) {
             SP.p[0] = std::max<u64>(1, Pw.npieces * (u64)spl / 256);
             SP.ncut = 1;
-            if (spl2 > spl && spl2 < 256) {
+            if (spl2 > spl) {
                 const u64 p1 = Pw.npieces * (u64)spl2 / 256;
                 if (p1 > SP.p[0] && p1 < Pw.npieces) SP.p[SP.ncut++] = p1;
             }
             for (u32 k = 0; k < SP.ncut; ++k) SP.x[k] = (SP.p[k] << WS_PIECE_SHIFT) - lead0;
-            SP.wait = sw >= 0 && sw <= 2 ? sw : 0;
-            SP.shift[0] = c0 >= 0 && c0 <= 6 ? (u32)c0 : 2u;
-            SP.shift[1] = c1 >= 0 && c1 <= 6 ? (u32)c1 : 1u;
-            if ((rc = slot.side(&SP.side, SP.ev, pr >= 0 && pr <= 2 ? pr : 0))) return rc;
+            SP.wait = ws_stream_split_wait;
+            SP.shift[0] = (u32)ws_stream_c0;
+            SP.shift[1] = (u32)ws_stream_c1;
+            if ((rc = slot.side(&SP.side, SP.ev, ws_stream_side_prio))) return rc;
         }
     }
+    const RwCall c{slot, d_buf, len, max_frames, d_desc, d_res, st, L, gen, Pw, d_seg, sd, A.state_ok,
+                   reinterpret_cast<unsigned char*>(A.d) + WS_AUX_HEAD, RL, A.gen, SP};
     if (dev_rw) {
         // a replay whose previous replay's chunk walk saw lengths that keep changing skips the
         // rounds on the device (they exit at once) and the plan kernel starts the walk at 0
         if ((rc = rounds(nr, false, 0, 1))) return rc;
-        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 2, d_seg, nullptr, &SP)))
-            return rc;
-        *A.state_ok = true;
-        return rw_unmask(L, Pw, gen, &SP, rw_plan);
+        return c.walk_device_unmask(RW_START_BY_DEVICE_HINT, nullptr);
     }
     if (!host_rw) {
         if ((rc = rounds(nr, true, 0, 0))) return rc;
@@ -1691,9 +1664,7 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     if (rw_opt == 1 && __atomic_load_n(&hm->walk_hint, __ATOMIC_RELAXED) == 1) {
         ++ws_stat_stream_skips;
         *A.state_ok = true;
-        if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 1, d_seg, dm, &SP)))
-            return rc;
-        return rw_unmask(L, Pw, gen, &SP, rw_plan);
+        return c.walk_device_unmask(RW_START_AT_ZERO, dm);
     }
     u32 tag = ws_next_gen();
     if ((rc = rounds(1, false, tag, 0)) || (rc = published(tag))) return rc;
@@ -1705,13 +1676,10 @@ extern "C" WSFRAME_AMD_EXPORT int websocketframeStreamDecodeDevice(unsigned char
     if (hm->phase != SD_DONE) {
         const u64 P = hm->P;
         const u32 nf = hm->nf;
-        if (len - P >= RW_MIN && rw_opt == 1) {                              // lengths keep changing:
-            if ((rc = rw_walk_device(d_buf, len, max_frames, d_desc, Pw, d_res, st, sd, rw_w, RL, A.gen, 0, d_seg, dm,
-                                     &SP)))                                  // the device walks
-                return rc;
-            return rw_unmask(L, Pw, gen, &SP, rw_plan);
+        if (len - P >= RW_MIN && rw_opt == 1) {                              // lengths keep changing: the device walks
+            return c.walk_device_unmask(RW_START_AT_STATE, dm);
         } else if (len - P >= RW_MIN) {                                      // ... the host follows
-            if ((rc = rw_walk(slot, d_buf, len, P, nf, max_frames, d_desc, Pw, d_res, st))) return rc;
+            if ((rc = c.walk(P, nf))) return rc;
         } else {
             hipLaunchKernelGGL(ws_stream_finish_kernel, dim3(1), dim3(64), 0, st, d_buf, (u64)len, max_frames, d_desc,
                                Pw.items, Pw.ptr, Pw.npieces, Pw.nwork, d_res, sd);

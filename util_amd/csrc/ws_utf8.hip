@@ -300,7 +300,7 @@ extern "C" WSFRAME_AMD_TEXT_EXPORT int websocketframeBatchValidateTextDevice(
     int rc = slot.acquire(st);
     if (rc) return rc;
     void* p = nullptr;
-    if ((rc = slot.text_workspace(words * sizeof(u32), &p))) return rc;
+    if ((rc = slot.buffer(WS_BUF_TEXT, words * sizeof(u32), 0, &p))) return rc;
     u32* const ws = reinterpret_cast<u32*>(p);
     hipError_t e = hipMemsetAsync(ws + flag_off, 0, (size_t)nseg * sizeof(u32), st);
     if (e != hipSuccess) return ws_set_err("websocketframeBatchValidateTextDevice: memset", e);
