@@ -62,7 +62,12 @@ _proto = None
 HS_LIB_PATH = os.path.join(HERE, "libwsframe_amd_hs.so")
 HS_EXPORTS = ["websocketframeBatchHandshakeDevice", "websocketframeHandshakeHost"]
 _hs = None
-_options = {}            # options set through set_option(): the ctl, text, proto and hs libraries keep their own copies
+# libwsframe_amd_reply.so: everything libwsframe_amd_hs.so exports plus the WSFRAME_AMD_REPLY_EXPORT
+# entry points (include/wsframe_amd_reply.h)
+REPLY_LIB_PATH = os.path.join(HERE, "libwsframe_amd_reply.so")
+REPLY_EXPORTS = ["websocketframeBatchControlRepliesDevice", "websocketframeControlRepliesHost"]
+_reply = None
+_options = {}            # options set through set_option(): the ctl, text, proto, hs and reply libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -168,6 +173,8 @@ def set_option(name, value):
             _proto.websocketframeGpuSetOption(name.encode(), int(value))
         if _hs is not None:
             _hs.websocketframeGpuSetOption(name.encode(), int(value))
+        if _reply is not None:
+            _reply.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -300,6 +307,45 @@ def load_hs_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _hs = lib
+    return lib
+
+
+def load_reply_lib():
+    """libwsframe_amd_reply.so: websocketframeBatchControlRepliesDevice and
+    websocketframeControlRepliesHost next to the whole C ABI of libwsframe_amd_hs.so (decode, check,
+    reply on one workspace). A library of its own state, as load_hs_lib(): the options set so far
+    are applied when it loads and forwarded afterwards."""
+    global _reply
+    if _reply is not None:
+        return _reply
+    load_lib()
+    if not os.path.exists(REPLY_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_reply.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(REPLY_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchControlRepliesDevice.restype = i32
+    lib.websocketframeBatchControlRepliesDevice.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+    lib.websocketframeControlRepliesHost.restype = C.c_longlong
+    lib.websocketframeControlRepliesHost.argtypes = [vp, u64, vp, vp, u32, u32, vp, u32, vp, vp, vp, u64, vp]
+    lib.websocketframeBatchCheckProtocolDevice.restype = i32
+    lib.websocketframeBatchCheckProtocolDevice.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp]
+    lib.websocketframeBatchDecodeDevice.restype = i32
+    lib.websocketframeBatchDecodeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.websocketframeStreamDecodeDevice.restype = i32
+    lib.websocketframeStreamDecodeDevice.argtypes = [vp, u64, u32, vp, vp, vp]
+    lib.websocketframeBatchReassembleDeviceCtl.restype = i32
+    lib.websocketframeBatchReassembleDeviceCtl.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp,
+                                                           u32, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    lib.websocketframeGpuGetStat.restype = i32
+    lib.websocketframeGpuGetStat.argtypes = [C.c_char_p, C.POINTER(C.c_ulonglong)]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _reply = lib
     return lib
 
 

@@ -61,6 +61,13 @@ assert HS_DTYPE.itemsize == 32
 HS_NONE = 0xFFFFFFFF
 HS_RESP_WRITTEN, HS_RESP_NO_SPACE, HS_ERR_SEG_LEN = 1, 2, 4
 HS_ECHO_PROTOCOL = 1
+# include/wsframe_amd_reply.h: the result of batch_control_replies_device / control_replies_host, close kinds, flags, state
+REPLY_RES_DTYPE = np.dtype([("n_pong", "<u4"), ("close_kind", "<u4"), ("close_status", "<u4"), ("tx_len", "<u4")])
+assert REPLY_RES_DTYPE.itemsize == 16
+REPLY_CLOSE_NONE, REPLY_CLOSE_ECHO, REPLY_CLOSE_PROTOCOL, REPLY_CLOSE_CALLER = range(4)
+REPLY_WIRE_MASKED, REPLY_LAST_PING_ONLY = 4, 8
+REPLY_ST_CLOSE_SENT = 1
+REPLY_NONE = 0xFFFFFFFF
 assert DESC_DTYPE.itemsize == C.sizeof(WsDesc) == 32
 assert SEGRES_DTYPE.itemsize == C.sizeof(WsSegRes) == 16
 
@@ -261,6 +268,60 @@ def proto_step_host(state, b0, masked, datalen, body2=None, flags=0, rsv_allowed
     code = _lib.load_proto_lib().websocketframeProtoStepHost(C.byref(st), b0, int(masked), datalen, body2, flags,
                                                              rsv_allowed, max_message_size)
     return code, st.value
+
+
+def batch_control_replies_device(buf, seg_off, desc, res, max_frames, tx, tx_off, reply_res, flags=0, proto_res=None,
+                                 fail_status=None, mask_key=None, reply_state=None, tx_capacity=None, stream=None):
+    """websocketframeBatchControlRepliesDevice (libwsframe_amd_reply.so) on what a decode call and,
+    optionally, batch_check_protocol_device on the same stream just produced: buf (uint8, the wire),
+    seg_off (int64 nseg), desc (uint8 >= 32*nseg*max_frames), res (uint8 16*nseg); tx (uint8: the
+    reply bytes; 131 B per counted frame + 8 B per segment always suffice), tx_off (int64 nseg + 1:
+    segment s's reply is tx[tx_off[s]:tx_off[s+1]]), reply_res (uint8 16*nseg: REPLY_RES_DTYPE
+    records); proto_res (uint8 16*nseg, optional), fail_status (int32 nseg, optional), mask_key
+    (int32 nseg*(max_frames+1), optional: client role), reply_state (int32 nseg, in/out, optional:
+    the per-connection carry, zero when the connection starts). flags: REPLY_WIRE_MASKED after a
+    reassembly call, REPLY_LAST_PING_ONLY; tx_capacity defaults to tx.numel(); async on `stream`."""
+    nseg = seg_off.numel()
+    assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
+    assert res.numel() * res.element_size() >= 16 * nseg
+    assert reply_res.numel() * reply_res.element_size() >= 16 * nseg
+    assert tx_off.numel() * tx_off.element_size() >= 8 * (nseg + 1)
+    assert proto_res is None or proto_res.numel() * proto_res.element_size() >= 16 * nseg
+    assert fail_status is None or fail_status.numel() * fail_status.element_size() >= 4 * nseg
+    assert mask_key is None or mask_key.numel() * mask_key.element_size() >= 4 * nseg * (max_frames + 1)
+    assert reply_state is None or reply_state.numel() * reply_state.element_size() >= 4 * nseg
+    cap = (0 if tx is None else tx.numel()) if tx_capacity is None else tx_capacity
+    lib = _lib.load_reply_lib()
+    rc = lib.websocketframeBatchControlRepliesDevice(_ptr(buf), _ptr(seg_off), _ptr(desc), _ptr(res), nseg, max_frames,
+                                                     int(flags), _ptr(proto_res), _ptr(fail_status), _ptr(mask_key),
+                                                     _ptr(reply_state), _ptr(tx), int(cap), _ptr(tx_off), _ptr(reply_res),
+                                                     _stream(stream))
+    check(rc, "websocketframeBatchControlRepliesDevice", lib)
+
+
+def control_replies_host(buf, seg_off, desc, res, max_frames, flags=0, proto_res=None, fail_status=0, mask_key=None,
+                         state=0, tx_capacity=None):
+    """websocketframeControlRepliesHost on one segment: buf (numpy uint8), desc (DESC_DTYPE, the
+    segment's max_frames slots), res (one SEGRES_DTYPE record), proto_res (one PROTO_RES_DTYPE record
+    or None), mask_key (numpy uint32, max_frames + 1, or None), state (the carry in, or None: no
+    carry). Returns (reply length, the reply bytes that fit in tx_capacity, REPLY_RES_DTYPE record,
+    state out)."""
+    lib = _lib.load_reply_lib()
+    desc = np.ascontiguousarray(desc)
+    res = np.ascontiguousarray(res).reshape(1)
+    pr = None if proto_res is None else np.ascontiguousarray(proto_res).reshape(1)
+    keys = None if mask_key is None else np.ascontiguousarray(mask_key, dtype=np.uint32)
+    cap = 131 * max_frames + 8 if tx_capacity is None else tx_capacity
+    tx = np.zeros(max(1, cap), np.uint8)
+    out = np.zeros(1, REPLY_RES_DTYPE)
+    st = None if state is None else C.c_uint(state)
+    n = lib.websocketframeControlRepliesHost(buf.ctypes.data, int(seg_off), desc.ctypes.data, res.ctypes.data, max_frames,
+                                             int(flags), None if pr is None else pr.ctypes.data, int(fail_status),
+                                             None if keys is None else keys.ctypes.data,
+                                             None if st is None else C.addressof(st), tx.ctypes.data, cap, out.ctypes.data)
+    if n < 0:
+        check(-1, "websocketframeControlRepliesHost", lib)
+    return n, bytes(tx[:min(n, cap)]), out[0], None if st is None else st.value
 
 
 def batch_handshake_device(buf, seg_off, seg_len, hs, flags=0, accept=None, resp=None, resp_off=None, resp_cap=0,
