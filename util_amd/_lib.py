@@ -67,7 +67,13 @@ _hs = None
 REPLY_LIB_PATH = os.path.join(HERE, "libwsframe_amd_reply.so")
 REPLY_EXPORTS = ["websocketframeBatchControlRepliesDevice", "websocketframeControlRepliesHost"]
 _reply = None
-_options = {}            # options set through set_option(): the ctl, text, proto, hs and reply libraries keep their own copies
+# libwsframe_amd_send.so: everything libwsframe_amd_reply.so exports plus the WSFRAME_AMD_SEND_EXPORT
+# entry points (include/wsframe_amd_send.h)
+SEND_LIB_PATH = os.path.join(HERE, "libwsframe_amd_send.so")
+SEND_EXPORTS = ["websocketframeBatchSendDevice", "websocketframeBatchSendListFromMessagesDevice",
+                "websocketframeSendHost"]
+_send = None
+_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply and send libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -175,6 +181,8 @@ def set_option(name, value):
             _hs.websocketframeGpuSetOption(name.encode(), int(value))
         if _reply is not None:
             _reply.websocketframeGpuSetOption(name.encode(), int(value))
+        if _send is not None:
+            _send.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -346,6 +354,36 @@ def load_reply_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _reply = lib
+    return lib
+
+
+def load_send_lib():
+    """libwsframe_amd_send.so: websocketframeBatchSendDevice, websocketframeBatchSendListFromMessagesDevice
+    and websocketframeSendHost next to the whole C ABI of libwsframe_amd_reply.so (receive, reply and
+    send on one workspace). A library of its own state, as load_reply_lib(): the options set so far
+    are applied when it loads and forwarded afterwards."""
+    global _send
+    if _send is not None:
+        return _send
+    load_lib()
+    if not os.path.exists(SEND_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_send.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(SEND_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchSendDevice.restype = i32
+    lib.websocketframeBatchSendDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp]
+    lib.websocketframeBatchSendListFromMessagesDevice.restype = i32
+    lib.websocketframeBatchSendListFromMessagesDevice.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    lib.websocketframeSendHost.restype = C.c_longlong
+    lib.websocketframeSendHost.argtypes = [vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _send = lib
     return lib
 
 

@@ -127,7 +127,8 @@ struct WsBuf {
 };
 static const char* const g_buf_what[WS_BUF_KINDS] = {"hipMalloc(workspace)", "hipMalloc(encode workspace)",
                                                      "hipMalloc(text workspace)", "hipMalloc(protocol check workspace)",
-                                                     "hipMalloc(reply workspace)", "hipMalloc(aux workspace)"};
+                                                     "hipMalloc(reply workspace)", "hipMalloc(send workspace)",
+                                                     "hipMalloc(aux workspace)"};
 struct WsStreamWs {
     hipStream_t stream = nullptr;
     unsigned long long capture = 0; // capture id of the graph this slot belongs to (0: eager calls)

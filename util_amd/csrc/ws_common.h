@@ -341,6 +341,7 @@ enum WsBufKind {          // a slot's grow-on-demand device buffers
     WS_BUF_TEXT,          // the text validator (ws_utf8.hip: per-slot records + tile scan)
     WS_BUF_PROTO,         // the protocol check (ws_proto.hip: segment offsets + tile summaries)
     WS_BUF_REPLY,         // the control replies (ws_reply.hip: ws_reply.h's WsReplyLayout)
+    WS_BUF_SEND,          // the batch message send (ws_send.hip: ws_send.h's WsSendLayout)
     WS_BUF_AUX,           // auxiliary scratch (the stream path's chunk-parallel walk): handed out by aux()
     WS_BUF_KINDS
 };

@@ -68,6 +68,14 @@ REPLY_CLOSE_NONE, REPLY_CLOSE_ECHO, REPLY_CLOSE_PROTOCOL, REPLY_CLOSE_CALLER = r
 REPLY_WIRE_MASKED, REPLY_LAST_PING_ONLY = 4, 8
 REPLY_ST_CLOSE_SENT = 1
 REPLY_NONE = 0xFFFFFFFF
+# include/wsframe_amd_send.h: the message entry and the result of batch_send_device / send_host, its status values
+SEND_MSG_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u8"), ("type", "<u4"), ("reserved", "<u4")])
+assert SEND_MSG_DTYPE.itemsize == 24
+SEND_RES_DTYPE = np.dtype([("tx_len", "<u8"), ("n_frames", "<u8"), ("n_msgs", "<u4"), ("status", "<u4"),
+                           ("first_bad", "<u4"), ("reserved", "<u4")])
+assert SEND_RES_DTYPE.itemsize == 32
+SEND_SKIP = SEND_NONE = SEND_FRAG_DEFAULT = 0xFFFFFFFF
+SEND_OK, SEND_ERR_FRAGMENT_SIZE, SEND_ERR_RANGE = range(3)
 assert DESC_DTYPE.itemsize == C.sizeof(WsDesc) == 32
 assert SEGRES_DTYPE.itemsize == C.sizeof(WsSegRes) == 16
 
@@ -322,6 +330,70 @@ def control_replies_host(buf, seg_off, desc, res, max_frames, flags=0, proto_res
     if n < 0:
         check(-1, "websocketframeControlRepliesHost", lib)
     return n, bytes(tx[:min(n, cap)]), out[0], None if st is None else st.value
+
+
+def batch_send_device(src, msg, nmsg, max_msgs, tx, tx_off, send_res, frag_size=None, mask_key=None, msg_tx_off=None,
+                      tx_capacity=None, src_len=None, flags=0, stream=None):
+    """websocketframeBatchSendDevice (libwsframe_amd_send.so) on torch CUDA tensors: src (uint8, the
+    bodies), msg (uint8 >= 24*nseg*max_msgs: SEND_MSG_DTYPE records at s*max_msgs + i), nmsg (int32
+    nseg), frag_size (int32 nseg, optional: every connection's write_fragment_size), mask_key (int32
+    nseg*max_msgs, optional: client role); tx (uint8: the wire bytes; None with tx_capacity 0 sizes),
+    tx_off (int64 nseg + 1: connection s owns tx[tx_off[s]:tx_off[s+1]]), msg_tx_off (int64
+    nseg*max_msgs, optional), send_res (uint8 32*nseg: SEND_RES_DTYPE records). tx_capacity defaults
+    to tx.numel(), src_len to src.numel(); async on `stream`."""
+    nseg = nmsg.numel()
+    assert msg.numel() * msg.element_size() >= 24 * nseg * max_msgs
+    assert tx_off.numel() * tx_off.element_size() >= 8 * (nseg + 1)
+    assert send_res.numel() * send_res.element_size() >= 32 * nseg
+    assert frag_size is None or frag_size.numel() * frag_size.element_size() >= 4 * nseg
+    assert mask_key is None or mask_key.numel() * mask_key.element_size() >= 4 * nseg * max_msgs
+    assert msg_tx_off is None or msg_tx_off.numel() * msg_tx_off.element_size() >= 8 * nseg * max_msgs
+    cap = (0 if tx is None else tx.numel()) if tx_capacity is None else tx_capacity
+    lib = _lib.load_send_lib()
+    rc = lib.websocketframeBatchSendDevice(_ptr(src), int(src.numel() if src_len is None else src_len), _ptr(msg), _ptr(nmsg),
+                                           nseg, int(max_msgs), _ptr(frag_size), _ptr(mask_key), int(flags), _ptr(tx),
+                                           int(cap), _ptr(tx_off), _ptr(msg_tx_off), _ptr(send_res), _stream(stream))
+    check(rc, "websocketframeBatchSendDevice", lib)
+
+
+def batch_send_list_from_messages_device(desc, msg, nmsg, max_frames, send_msg, stream=None):
+    """websocketframeBatchSendListFromMessagesDevice: the echo's send list (uint8 >= 24*nseg*max_frames)
+    from what batch_reassemble_device left in desc, msg and nmsg; async on `stream`."""
+    nseg = nmsg.numel()
+    assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
+    assert msg.numel() * msg.element_size() >= 32 * nseg * max_frames
+    assert send_msg.numel() * send_msg.element_size() >= 24 * nseg * max_frames
+    lib = _lib.load_send_lib()
+    rc = lib.websocketframeBatchSendListFromMessagesDevice(_ptr(desc), _ptr(msg), _ptr(nmsg), nseg, int(max_frames),
+                                                           _ptr(send_msg), _stream(stream))
+    check(rc, "websocketframeBatchSendListFromMessagesDevice", lib)
+
+
+def send_host(src, msg, frag_size=SEND_FRAG_DEFAULT, mask_key=None, tx_capacity=None, flags=0):
+    """websocketframeSendHost on one connection: src (numpy uint8), msg (SEND_MSG_DTYPE array),
+    mask_key (numpy uint32, one per message, or None). Returns (full length, the wire bytes that
+    fit in tx_capacity, every message's offset, SEND_RES_DTYPE record)."""
+    lib = _lib.load_send_lib()
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    msg = np.ascontiguousarray(msg, dtype=SEND_MSG_DTYPE)
+    keys = None if mask_key is None else np.ascontiguousarray(mask_key, dtype=np.uint32)
+    out = np.zeros(1, SEND_RES_DTYPE)
+    moff = np.zeros(max(1, len(msg)), np.uint64)
+    pad = np.zeros(1, np.uint8)
+    sp = src.ctypes.data if len(src) else pad.ctypes.data
+    if tx_capacity is None:
+        tx_capacity = lib.websocketframeSendHost(sp, len(src), msg.ctypes.data, len(msg), int(frag_size),
+                                                 None if keys is None else keys.ctypes.data, int(flags), None, 0, None,
+                                                 out.ctypes.data)
+        if tx_capacity < 0:
+            check(-1, "websocketframeSendHost", lib)
+    tx = np.zeros(max(1, tx_capacity), np.uint8)
+    n = lib.websocketframeSendHost(sp, len(src), msg.ctypes.data, len(msg), int(frag_size),
+                                   None if keys is None else keys.ctypes.data, int(flags), tx.ctypes.data, tx_capacity,
+                                   moff.ctypes.data, out.ctypes.data)
+    if n < 0:
+        check(-1, "websocketframeSendHost", lib)
+    return n, bytes(tx[:min(n, tx_capacity)]), moff[:len(msg)], out[0]
 
 
 def batch_handshake_device(buf, seg_off, seg_len, hs, flags=0, accept=None, resp=None, resp_off=None, resp_cap=0,
