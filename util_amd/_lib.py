@@ -73,7 +73,13 @@ SEND_LIB_PATH = os.path.join(HERE, "libwsframe_amd_send.so")
 SEND_EXPORTS = ["websocketframeBatchSendDevice", "websocketframeBatchSendListFromMessagesDevice",
                 "websocketframeSendHost"]
 _send = None
-_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply and send libraries keep their own copies
+# libwsframe_amd_cli.so: everything libwsframe_amd_send.so exports plus the WSFRAME_AMD_CLI_EXPORT
+# entry points (include/wsframe_amd_client.h)
+CLI_LIB_PATH = os.path.join(HERE, "libwsframe_amd_cli.so")
+CLI_EXPORTS = ["websocketframeBatchClientRequestDevice", "websocketframeBatchClientVerifyDevice",
+               "websocketframeClientRequestHost", "websocketframeClientVerifyHost"]
+_cli = None
+_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply, send and cli libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -183,6 +189,8 @@ def set_option(name, value):
             _reply.websocketframeGpuSetOption(name.encode(), int(value))
         if _send is not None:
             _send.websocketframeGpuSetOption(name.encode(), int(value))
+        if _cli is not None:
+            _cli.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -384,6 +392,43 @@ def load_send_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _send = lib
+    return lib
+
+
+def load_cli_lib():
+    """libwsframe_amd_cli.so: the client handshake (websocketframeBatchClientRequestDevice,
+    websocketframeBatchClientVerifyDevice and their host twins) next to the whole C ABI of
+    libwsframe_amd_send.so (a connection opened in either role on one library). A library of its
+    own state, as load_send_lib(): the options set so far are applied when it loads and forwarded
+    afterwards."""
+    global _cli
+    if _cli is not None:
+        return _cli
+    load_lib()
+    if not os.path.exists(CLI_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_cli.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(CLI_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchClientRequestDevice.restype = i32
+    lib.websocketframeBatchClientRequestDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.websocketframeBatchClientVerifyDevice.restype = i32
+    lib.websocketframeBatchClientVerifyDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, u64, vp, u32, vp, vp]
+    lib.websocketframeClientRequestHost.restype = i32
+    lib.websocketframeClientRequestHost.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp]
+    lib.websocketframeClientVerifyHost.restype = i32
+    lib.websocketframeClientVerifyHost.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp]
+    lib.websocketframeBatchHandshakeDevice.restype = i32
+    lib.websocketframeBatchHandshakeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, u32, vp]
+    lib.websocketframeBatchDecodeDevice.restype = i32
+    lib.websocketframeBatchDecodeDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _cli = lib
     return lib
 
 

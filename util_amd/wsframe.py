@@ -76,6 +76,19 @@ SEND_RES_DTYPE = np.dtype([("tx_len", "<u8"), ("n_frames", "<u8"), ("n_msgs", "<
 assert SEND_RES_DTYPE.itemsize == 32
 SEND_SKIP = SEND_NONE = SEND_FRAG_DEFAULT = 0xFFFFFFFF
 SEND_OK, SEND_ERR_FRAGMENT_SIZE, SEND_ERR_RANGE = range(3)
+# include/wsframe_amd_client.h: the entry, the two descriptors, the flags and the reasons of the client handshake
+CLI_ENTRY_DTYPE = np.dtype([("path_off", "<u8"), ("proto_off", "<u8"), ("host_off", "<u8"), ("path_len", "<u4"),
+                            ("proto_len", "<u4"), ("host_len", "<u4"), ("reserved", "<u4", (3,))])
+assert CLI_ENTRY_DTYPE.itemsize == 48
+CLI_REQ_DTYPE = np.dtype([("req_len", "<u4"), ("key_off", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert CLI_REQ_DTYPE.itemsize == 16
+CLI_VERIFY_DTYPE = np.dtype([("ret", "<i4"), ("reason", "<u4"), ("status", "<u4"), ("proto_off", "<u4"), ("proto_len", "<u4"),
+                             ("accept_off", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert CLI_VERIFY_DTYPE.itemsize == 32
+CLI_NONE = 0xFFFFFFFF
+CLI_REQ_WRITTEN, CLI_REQ_NO_SPACE, CLI_ERR_RANGE, CLI_ERR_BYTES, CLI_ERR_SEG_LEN = 1, 2, 4, 8, 16
+(CLI_OK, CLI_REASON_STATUS, CLI_REASON_UPGRADE, CLI_REASON_CONNECTION, CLI_REASON_ACCEPT, CLI_REASON_EXTENSION,
+ CLI_REASON_PROTOCOL, CLI_REASON_TOO_LONG) = range(8)
 assert DESC_DTYPE.itemsize == C.sizeof(WsDesc) == 32
 assert SEGRES_DTYPE.itemsize == C.sizeof(WsSegRes) == 16
 
@@ -436,6 +449,78 @@ def handshake_host(data, flags=0, resp_cap=512, want_accept=True, want_resp=True
     ok = int(d["ret"]) > 0
     return (d, bytes(acc[:28]) if ok and want_accept else None,
             bytes(resp[:int(d["resp_len"])]) if int(d["flags"]) & HS_RESP_WRITTEN else None)
+
+
+def batch_client_request_device(strs, entry, nonce, req, expect, rd, req_off=None, req_cap=0, flags=0, stream=None):
+    """websocketframeBatchClientRequestDevice (libwsframe_amd_cli.so) on torch CUDA tensors: strs (uint8
+    string pool), entry (uint8 48*nseg: CLI_ENTRY_DTYPE records), nonce (uint8 16*nseg), req (uint8)
+    with slots at req_off (int64 nseg) or s*req_cap, expect (uint8 32*nseg), rd (uint8 16*nseg:
+    CLI_REQ_DTYPE records); async on `stream`."""
+    nseg = entry.numel() * entry.element_size() // CLI_ENTRY_DTYPE.itemsize
+    assert nonce.numel() >= 16 * nseg and expect.numel() >= 32 * nseg and rd.numel() * rd.element_size() >= 16 * nseg
+    assert req is None or req_off is not None or req.numel() >= nseg * req_cap
+    assert req_off is None or req_off.numel() >= nseg
+    lib = _lib.load_cli_lib()
+    rc = lib.websocketframeBatchClientRequestDevice(_ptr(strs), strs.numel(), _ptr(entry), _ptr(nonce), nseg, int(flags),
+                                                    _ptr(req), _ptr(req_off), int(req_cap), _ptr(expect), _ptr(rd),
+                                                    _stream(stream))
+    check(rc, "websocketframeBatchClientRequestDevice", lib)
+
+
+def batch_client_verify_device(buf, seg_off, seg_len, expect, cv, strs=None, entry=None, max_head=0, flags=0, stream=None,
+                               buflen=None):
+    """websocketframeBatchClientVerifyDevice (libwsframe_amd_cli.so) on torch CUDA tensors: buf (uint8,
+    only read; the last BATCH_PAD bytes are slack), seg_off/seg_len (int64 nseg), expect (uint8
+    32*nseg, as the request call wrote it), cv (uint8 32*nseg: CLI_VERIFY_DTYPE records), strs and
+    entry (optional: the offered subprotocols); async on `stream`. buflen defaults to
+    buf.numel() - BATCH_PAD."""
+    nseg = seg_off.numel()
+    assert seg_len.numel() == nseg and cv.numel() * cv.element_size() >= 32 * nseg and expect.numel() >= 32 * nseg
+    assert entry is None or (strs is not None and entry.numel() * entry.element_size() >= 48 * nseg)
+    if buflen is None:
+        assert buf.numel() >= BATCH_PAD, "device batch needs WEBSOCKET_BATCH_PAD bytes of slack"
+        buflen = buf.numel() - BATCH_PAD
+    lib = _lib.load_cli_lib()
+    rc = lib.websocketframeBatchClientVerifyDevice(_ptr(buf), int(buflen), _ptr(seg_off), _ptr(seg_len), nseg, int(flags),
+                                                   _ptr(expect), _ptr(strs), 0 if strs is None else strs.numel(),
+                                                   _ptr(entry), int(max_head), _ptr(cv), _stream(stream))
+    check(rc, "websocketframeBatchClientVerifyDevice", lib)
+
+
+def client_request_host(path, nonce, proto=b"", host=b"", req_cap=4096, want_req=True, flags=0):
+    """websocketframeClientRequestHost for one connection (bytes): returns (CLI_REQ_DTYPE record,
+    request bytes or None, expect bytes (32) or None)."""
+    lib = _lib.load_cli_lib()
+    assert len(nonce) == 16
+    arr = [np.frombuffer(bytes(b) + b"\0", np.uint8).copy() for b in (path, proto, host, nonce)]
+    rd = np.zeros(1, CLI_REQ_DTYPE)
+    req = np.zeros(max(1, req_cap), np.uint8)
+    expect = np.zeros(32, np.uint8)
+    rc = lib.websocketframeClientRequestHost(arr[0].ctypes.data, len(path), arr[1].ctypes.data, len(proto),
+                                             arr[2].ctypes.data, len(host), arr[3].ctypes.data, int(flags),
+                                             req.ctypes.data if want_req else None, int(req_cap), expect.ctypes.data,
+                                             rd.ctypes.data)
+    check(rc, "websocketframeClientRequestHost", lib)
+    d = rd[0]
+    err = int(d["flags"]) & (CLI_ERR_RANGE | CLI_ERR_BYTES)
+    return (d, bytes(req[:int(d["req_len"])]) if int(d["flags"]) & CLI_REQ_WRITTEN else None,
+            None if err else bytes(expect))
+
+
+def client_verify_host(data, expect, offered=b"", max_head=0, flags=0):
+    """websocketframeClientVerifyHost on one response (bytes): returns the CLI_VERIFY_DTYPE record. The
+    response is copied into a buffer with BATCH_PAD bytes after it."""
+    lib = _lib.load_cli_lib()
+    buf = np.zeros(len(data) + BATCH_PAD, np.uint8)
+    buf[:len(data)] = np.frombuffer(bytes(data), np.uint8)
+    ex = np.frombuffer(bytes(expect).ljust(32, b"\0"), np.uint8).copy()
+    of = np.frombuffer(bytes(offered) + b"\0", np.uint8).copy()
+    cv = np.zeros(1, CLI_VERIFY_DTYPE)
+    rc = lib.websocketframeClientVerifyHost(buf.ctypes.data, len(data), int(flags), ex.ctypes.data,
+                                            of.ctypes.data if offered else None, len(offered), int(max_head),
+                                            cv.ctypes.data)
+    check(rc, "websocketframeClientVerifyHost", lib)
+    return cv[0]
 
 
 def batch_encode_device(src, frames, dst, wire_off, capacity=None, stream=None):
