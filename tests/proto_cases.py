@@ -11,6 +11,7 @@ from oracle_lib import oracle_segments
 PAD = 32                                                  # WEBSOCKET_BATCH_PAD
 KEY = bytes([0x37, 0xFA, 0x21, 0x3D])                     # RFC 6455 5.7's example key
 CONT, TEXT, BIN, CLOSE, PING, PONG = 0, 1, 2, 8, 9, 10
+NO_BODY = (1 << 64) - 1                                   # the data_off of a frame without a body
 
 
 def frame(op, body=b"", fin=1, rsv=0, masked=True, key=KEY):
@@ -68,6 +69,61 @@ class Batch:
     def expect(self, flags=0, rsv_allowed=0, limit=0, state=None):
         wire = self.raw if flags & P.WIRE_MASKED else self.dec
         return P.check(wire, self.seg_off, self.desc, self.res, self.max_frames, flags, rsv_allowed, limit, state)
+
+
+class Tiled:
+    """nseg segments: the segments of the Batch `p`, one period, laid end to end again and again
+    and cut after nseg. A Batch's attributes, made by numpy from p's (a descriptor's offsets move
+    with its copy of the wire), so that a batch too large for the per-frame builders and oracles
+    costs one period of them. tile() repeats any per-segment array of the period the same way;
+    expect() is the period's oracle answer repeated, which is exact as long as no state is carried
+    in: every segment then stands alone."""
+
+    def __init__(self, p, nseg):
+        self.p, self.nseg, self.max_frames = p, nseg, p.max_frames
+        self.reps = -(-nseg // p.nseg)
+        span = len(p.raw) - PAD                               # one period's wire
+        self.raw = np.concatenate([np.tile(p.raw[:span], self.reps), p.raw[span:]])
+        self.dec = np.concatenate([np.tile(p.dec[:span], self.reps), p.dec[span:]])
+        base = np.repeat(np.arange(self.reps, dtype=np.uint64) * np.uint64(span), p.nseg)[:nseg]   # each segment's copy
+        self.seg_off = self.tile(np.asarray(p.seg_off, np.uint64)) + base
+        self.seg_len = self.tile(np.asarray(p.seg_len, np.uint64))
+        self.res = self.tile(p.res)
+        self.desc = self.tile(p.desc, p.max_frames)
+        counted = (np.arange(p.max_frames)[None, :] < self.res["n_frames"][:, None]).reshape(-1)
+        move = np.repeat(base, p.max_frames) * counted.astype(np.uint64)
+        self.desc["frame_off"] += move
+        self.desc["data_off"] += move * (self.desc["data_off"] != np.uint64(NO_BODY)).astype(np.uint64)
+
+    def tile(self, a, per=1):
+        """an array of the period with `per` entries a segment, for the nseg segments"""
+        return np.tile(a, self.reps)[:self.nseg * per].copy()
+
+    def expect(self, flags=0, rsv_allowed=0, limit=0, state=None):
+        assert state is None or not np.any(state)
+        codes, res, words = self.p.expect(flags, rsv_allowed, limit, None if state is None else np.zeros(self.p.nseg, np.uint64))
+        return self.tile(codes, self.max_frames), self.tile(res), None if words is None else self.tile(words)
+
+
+def one_frame_period():
+    """seven segments that count one frame under max_frames 1: a message left open (its second
+    frame is cut off by max_frames), a continuation of nothing, a CLOSE with a status that may not
+    be sent, pings with and without a body, a message, a CLOSE"""
+    return [[frame(TEXT, b"a", fin=0), frame(CONT, b"b")], [frame(CONT, b"c")], [close(1005)], [frame(PING, b"pq")],
+            [frame(BIN, b"xyz")], [close(1000, b"bye")], [frame(PING)]]
+
+
+def long_period():
+    """six segments of 765 to 769 frames (4607 in all: the period moves by 255 list positions), each
+    three tiles long and more, whose answers need what the tiles before bring along: a message of
+    769 one-byte fragments (a limit of 700 bytes stops its frame 700), a message left open over
+    500 frames that a TEXT frame then interrupts, a CLOSE at frame 400 with pings before and after
+    it, a segment that ends inside a message, a CLOSE with status 1005 as the last of 769 frames,
+    a quiet one"""
+    text = [frame(TEXT, b"a", fin=0)] + [frame(CONT, b"b", fin=0) for _ in range(768)]
+    return [text, quiet(500, tail_open=True) + [frame(PING, b"still open"), error_frame(9, True, 0)] + quiet(266),
+            quiet(400) + [close(1000)] + quiet(367) + [close(1005)], quiet(767, tail_open=True), quiet(768) + [close(1005)],
+            quiet(765)]
 
 
 # ---------------------------------------------------------------------------------------------

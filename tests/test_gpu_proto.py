@@ -271,6 +271,35 @@ def test_max_frames_one(dev):
     run_batch(dev, b, 0, 0, 0, state, "max_frames 1")
 
 
+def test_more_than_1024_plan_blocks(dev):
+    """262 145 one-frame segments under max_frames 1: 1025 plan blocks of 256 segments (and 1025
+    tiles), so every thread of the one-block scan of the block sums takes two of them. The batch
+    is a period of seven segments repeated (PC.Tiled), every segment compared."""
+    b = PC.Tiled(PC.Batch(PC.one_frame_period(), 1, gap=3), 262145)
+    state = np.zeros(b.nseg, np.uint64)
+    exp = b.expect(EM, 0, 0, state)
+    assert [int(c) for c in exp[1]["code"][:7]] == [0, 8, 7, 0, 0, 0, 0] and exp[2][0] == P.ST_OPEN | 1
+    assert [int(c) for c in exp[1]["close_frame"][:7]] == [P.NONE, P.NONE, 0, P.NONE, P.NONE, 0, P.NONE]
+    run_batch(dev, b, EM, 0, 0, state, "1025 plan blocks")
+
+
+def test_more_than_1024_tiles(dev):
+    """342 segments of 765 to 769 frames, 1026 tiles: every thread of the one-block scan of the tile
+    summaries takes two of them. A period of six segments repeated (PC.Tiled), each three tiles
+    long and more and 255 list positions further on in every period, so the tile edges fall
+    everywhere; the error behind 700 bytes of an open message, the open message a TEXT frame
+    interrupts, the frames after a CLOSE and the state words all need the tiles before."""
+    b = PC.Tiled(PC.Batch(PC.long_period(), 769, gap=2), 342)
+    assert int(PC.list_starts(b)[-1]) + int(b.res["n_frames"][-1]) > 1024 * 256
+    state = np.zeros(b.nseg, np.uint64)
+    exp = b.expect(EM, 0, 700, state)
+    assert [int(f) for f in exp[1]["first_bad"][:6]] == [700, 501, P.NONE, P.NONE, 768, P.NONE]
+    assert [int(c) for c in exp[1]["code"][:6]] == [10, 9, 0, 0, 7, 0] and int(exp[1]["close_frame"][2]) == 400
+    assert (exp[0][2 * 769 + 401:3 * 769] == P.AFTER_CLOSE).all()
+    assert [int(w) for w in exp[2][:6]] == [P.ST_OPEN | 769, 0, P.ST_CLOSED, P.ST_OPEN | 2, P.ST_CLOSED, 0]
+    run_batch(dev, b, EM, 0, 700, state, "1026 tiles")
+
+
 # ------------------------------------------------------------------ 4: frames that are not consumed
 
 def test_not_consumed(dev):

@@ -247,6 +247,47 @@ def test_pings_span_three_tiles_close_in_the_last(dev):
     run_case(dev, c, "three tiles, first_bad 600")
 
 
+def tiled_case(period, nseg, keyed):
+    """(Case, the model's answer) of nseg segments: the Batch `period` repeated (PC.Tiled), a state
+    word of 0 per segment, the keys of one period repeated when keyed. The model runs on one
+    period; its per-segment answers are repeated and d_tx_off is the running sum of the repeated
+    lengths, which is exact: every segment stands alone."""
+    b = PC.Tiled(period, nseg)
+    mf = b.max_frames
+    pkeys = np.random.default_rng(7).integers(0, 1 << 32, period.nseg * (mf + 1), dtype=np.uint64).astype(np.uint32) if keyed else None
+    tx, off, res, st = RC.Case(period, 0, None, None, pkeys, np.zeros(period.nseg, np.uint32)).expect()
+    rest = int(off[nseg % period.nseg])
+    exp = (tx * (nseg // period.nseg) + tx[:rest], np.concatenate([[0], np.cumsum(b.tile(np.diff(off)))]).astype(np.uint64),
+           b.tile(res), b.tile(st))
+    return RC.Case(b, 0, None, None, None if pkeys is None else b.tile(pkeys, mf + 1), np.zeros(nseg, np.uint32)), exp
+
+
+@pytest.mark.parametrize("keyed", [False, True])
+def test_more_than_1024_tiles(dev, keyed):
+    """342 segments of 765 to 769 frames, 1026 tiles (tests/test_gpu_proto.py's batch): every thread
+    of the one-block scan of the tile summaries takes two of them; a PONG's offset and what a
+    segment sends need the tiles before. Pings stand before and after the CLOSE at frame 400."""
+    period = PC.Batch(PC.long_period(), 769, gap=2)
+    c, exp = tiled_case(period, 342, keyed)
+    assert int(PC.list_starts(c.b)[-1]) + int(c.b.res["n_frames"][-1]) > 1024 * 256
+    pings = [sum(1 for f in seg[:stop] if f[0] == 0x89) for seg, stop in zip(PC.long_period(), (769, 768, 400, 767, 768, 765))]
+    assert pings[2] > 30 and sum(1 for f in PC.long_period()[2][401:] if f[0] == 0x89) > 30
+    assert [tuple(int(v) for v in r)[:3] for r in exp[2][:6]] == [
+        (pings[0], 0, 0), (pings[1], 0, 0), (pings[2], R.CLOSE_ECHO, 1000), (pings[3], 0, 0), (pings[4], R.CLOSE_ECHO, 1005),
+        (pings[5], 0, 0)]
+    run_case(dev, c, "1026 tiles keyed %d" % keyed, expect=exp)
+
+
+def test_more_than_1024_plan_blocks(dev):
+    """262 145 one-frame segments under max_frames 1: 1025 blocks of 256 segments, so every thread
+    of the one-block scans of the frame counts and of the reply lengths takes two block sums"""
+    c, exp = tiled_case(PC.Batch(PC.one_frame_period(), 1, gap=3), 262145, False)
+    assert [tuple(int(v) for v in r) for r in exp[2][:7]] == [
+        (0, 0, 0, 0), (0, 0, 0, 0), (0, R.CLOSE_ECHO, 1005, 4), (1, 0, 0, 4), (0, 0, 0, 0), (0, R.CLOSE_ECHO, 1000, 4), (1, 0, 0, 2)]
+    assert [int(v) for v in exp[3][:7]] == [0, 0, 1, 0, 0, 1, 0]
+    run_case(dev, c, "1025 plan blocks", expect=exp)
+
+
 # ------------------------------------------------------------------ 4: packing
 
 @pytest.mark.parametrize("nseg", [1, 3, 64, 65, 1000])

@@ -135,6 +135,38 @@ def test_1000_connections_of_mixed_lists(dev, src):
         assert st == {0, 1, 2}
 
 
+PERIOD_1 = [[(11, 5, 2)], [], [(700, 0, 1)], [(3, 9, S.SKIP)], [(SC.SRC_LEN, 1, 2)], [(4321, 20, 1)], [(99, 13, 2)]]
+PERIOD_3 = [[(11, 5, 2), (40, 20, 1), (7, 0, 2)], [], [(700, 17, 1)], [(3, 9, S.SKIP), (5, 1, 2)], [(8, 3, 1), (SC.SRC_LEN - 1, 2, 2), (9, 4, 2)],
+            [(4321, 20, 1), (1, 1, S.SKIP), (77, 11, 1)], [(99, 13, 2), (100, 2, 2)]]
+
+
+@pytest.mark.parametrize("role", [False, True])
+@pytest.mark.parametrize("nseg,max_msgs,period", [(262145, 1, PERIOD_1), (87382, 3, PERIOD_3)])
+def test_more_than_1024_blocks_and_tiles(dev, src, role, nseg, max_msgs, period):
+    """262 145 connections of one slot: 1025 blocks of 256 connections, so every thread of the
+    one-block scan of the block sums (u64) takes two; 87 382 connections of three slots: 1025 tiles
+    with connections across the tile edges, so every thread of the one-block scan of the tile
+    summaries takes two. Messages of 0 to 20 bytes, SKIP entries, a range error, and a fragment
+    size that carries no byte on the last connection of the period of seven, which is repeated. The
+    model runs on one period; its per-connection answers are repeated and the offsets are the
+    running sum of the repeated lengths, which is exact: a connection stands alone."""
+    P = len(period)
+    reps, rest = nseg // P, nseg % P
+    tile = lambda a, per=1: np.tile(a, reps + 1)[:nseg * per]
+    pfrags = [S.FRAG_DEFAULT, 130, S.FRAG_DEFAULT, 50, S.FRAG_DEFAULT, 16, 2]
+    pkeys = SC.keys_for(dict(role=role, conns=period), max_msgs)
+    ptx, poff, pmoff, pres = S.batch(src, period, pfrags, pkeys, max_msgs)
+    assert [int(v) for v in pres["status"]] == [0, 0, 0, 0, S.ERR_RANGE, 0, S.ERR_FRAGMENT_SIZE] and int(poff[-1]) > 0
+    off = np.concatenate([[0], np.cumsum(tile(np.diff(poff.astype(np.int64))))]).astype(np.uint64)
+    moff = tile(pmoff - np.repeat(poff[:-1], max_msgs), max_msgs) + np.repeat(off[:-1], max_msgs)
+    moff[tile(pmoff, max_msgs) == NONE64] = NONE64            # the slots past a connection's count
+    exp = (np.concatenate([np.tile(ptx, reps), ptx[:int(poff[rest])]]), off, moff, tile(pres))
+    assert len(exp[0]) == int(off[-1]) < 8 << 20
+    c = Call(dev, src, (period * (reps + 1))[:nseg], tile(pfrags), None if pkeys is None else tile(pkeys, max_msgs), max_msgs, exp=exp)
+    c.run()
+    c.check("%d connections of %d, role %d" % (nseg, max_msgs, role))
+
+
 @pytest.mark.parametrize("role", [False, True])
 def test_source_phases_and_fan_out(dev, src, role):
     """src_off at all 16 phases (and d_tx at several), then one body fanned out to 64 connections"""

@@ -475,6 +475,28 @@ def test_one_large_message(dev):
     assert ev[0].elapsed_time(ev[1]) < 2000.0
 
 
+def test_more_than_1024_plan_blocks(dev):
+    """1021 segments of 257 slots: 262 397 slots in 1025 plan blocks, so every thread of the
+    one-block scan of the block sums takes two. A segment lists 0 to 40 messages of a few bytes
+    (the counts turn with a period of seven segments, the bodies with one of ten messages), and
+    its slots move by one through the blocks from segment to segment: valid, invalid and
+    unfinished text, binary messages, CLOSE reasons, the last message left open here and there."""
+    bodies = [b"", b"a", SEQS[2], SEQS[3] + b"x", SEQS[4], b"\xc2", b"ab\xff", SEQS[3][:2], b"\xed\xa0\x80", "wörld".encode()]
+    counts = [3, 0, 40, 1, 7, 18, 5]
+    nseg, mf = 1021, 257
+    assert (nseg * mf + 255) // 256 == 1025
+    segs = []
+    for s in range(nseg):
+        ms = [(2 if (s + i) % 5 == 4 else 1, bodies[(3 * s + i) % len(bodies)], 1, 0, 1) for i in range(counts[s % 7])]
+        if ms and s % 7 in (2, 4):
+            ms[-1] = ms[-1][:2] + (0, 0, 1)                    # left open
+        if s % 7 == 6:
+            ms[1] = (8, b"\x03\xe8" + ms[1][1], 1, 0, 1)       # a CLOSE: its reason is checked
+        segs.append(ms)
+    gv = direct(dev, segs, mf, state=torch.zeros(nseg, dtype=torch.int32, device=dev), tag="1025 plan blocks")
+    assert all((gv[:, :40] == v).any() for v in (T.VALID, T.INVALID, T.NA))
+
+
 # ------------------------------------------------------------------ graph capture, workspace
 
 def test_capture_and_workspace(dev):

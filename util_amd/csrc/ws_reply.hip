@@ -3,8 +3,9 @@
 // the descriptors a decode call produced, for gfx950. The rule, the run summary and its combine,
 // the frame writer and the workspace layout are ws_reply.h's (one definition, host-tested).
 //
-// Work is divided as in ws_proto.hip: the counted frames of all segments, laid end to end in
-// segment order, form one list; a tile is 256 consecutive frames of it, one per thread.
+// Work is divided by frames: the counted frames of all segments, laid end to end in segment
+// order, form one list; a tile is 256 consecutive frames of it, one per thread. The plan, the
+// list, the tile scan and the carries are ws_scan.h's (one definition).
 //   plan     one thread per segment: its frame count, the exclusive scan of the counts inside its
 //            block of 256 segments and the block's sum;
 //   scan     one block: exclusive scan of the block sums, the total;
@@ -24,8 +25,8 @@
 // Every output is written with plain vector stores.
 #include <stdio.h>
 
-#include "ws_common.h"
 #include "ws_reply.h"
+#include "ws_scan.h"
 
 #define REPLY_T 256                      // threads per block: frames per tile, segments per plan block
 #define REPLY_BLOCKS_PER_CU 8            // the tile kernels' grid
@@ -36,111 +37,22 @@ static_assert(REPLY_T == WS_REPLY_T && sizeof(WsReplySum) == 32 && sizeof(WsRepl
 static_assert(WEBSOCKET_REPLY_WIRE_MASKED == WEBSOCKET_PROTO_WIRE_MASKED && WS_REPLY_NONE == WEBSOCKET_PROTO_NONE,
               "wsframe_amd_reply.h and wsframe_amd_proto.h agree");
 
-__device__ __forceinline__ WsReplySum reply_ld(const WsReplySum* p) {
-    const gu32x4* const g = gptr<u32x4>(p);
-    const u32x4 a = g[0], b = g[1];
-    return WsReplySum{a.x, a.y, a.z, a.w, (u64)b.x | (u64)b.y << 32, b.z, 0u};
-}
-__device__ __forceinline__ void reply_st(WsReplySum* p, const WsReplySum& s) {
-    u32x4 a, b;
-    a.x = s.bits; a.y = s.close; a.z = s.npong; a.w = s.last;
-    b.x = (u32)s.bytes; b.y = (u32)(s.bytes >> 32); b.z = s.last_bytes; b.w = 0u;
-    gu32x4* const g = gptr<u32x4>(p);
-    g[0] = a;
-    g[1] = b;
-}
-__device__ __forceinline__ WsReplyRec rec_ld(const WsReplyRec* p) {
-    const gu32x4* const g = gptr<u32x4>(p);
-    const u32x4 a = g[0], b = g[1];
-    return WsReplyRec{(u64)a.x | (u64)a.y << 32, (u64)a.z | (u64)a.w << 32, b.x, b.y, b.z, 0u};
-}
-__device__ __forceinline__ void rec_st(WsReplyRec* p, const WsReplyRec& r) {
-    u32x4 a, b;
-    a.x = (u32)r.loc_off; a.y = (u32)(r.loc_off >> 32); a.z = (u32)r.pong_bytes; a.w = (u32)(r.pong_bytes >> 32);
-    b.x = r.end; b.y = r.only; b.z = r.close; b.w = 0u;
-    gu32x4* const g = gptr<u32x4>(p);
-    g[0] = a;
-    g[1] = b;
-}
-__device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
-    return (u64)(u32)__shfl_up((int)(u32)v, d) | (u64)(u32)__shfl_up((int)(u32)(v >> 32), d) << 32;
-}
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-    return (u64)(u32)__shfl((int)(u32)v, src) | (u64)(u32)__shfl((int)(u32)(v >> 32), src) << 32;
-}
-__device__ __forceinline__ WsReplySum reply_shfl_up(const WsReplySum& s, int d) {
-    WsReplySum r;
-    r.bits = (u32)__shfl_up((int)s.bits, d);
-    r.close = (u32)__shfl_up((int)s.close, d);
-    r.npong = (u32)__shfl_up((int)s.npong, d);
-    r.last = (u32)__shfl_up((int)s.last, d);
-    r.bytes = shfl_up64(s.bytes, d);
-    r.last_bytes = (u32)__shfl_up((int)s.last_bytes, d);
-    r.pad = 0u;
-    return r;
-}
-
-// Segmented scan (ws_reply_comb_seg) over the block's REPLY_T values in thread order: *excl takes
-// the fold of the values before this thread, the fold of all of them is returned.
-__device__ __forceinline__ WsReplySum reply_block_scan(WsReplySum v, WsReplySum* wsum, WsReplySum* excl) {
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const WsReplySum o = reply_shfl_up(v, d);
-        if (lane >= (u32)d) v = ws_reply_comb_seg(o, v);
-    }
-    WsReplySum e = reply_shfl_up(v, 1);
-    if (lane == 0) e = ws_reply_sum_none();
-    __syncthreads();                                   // (the previous tile's readers of wsum are done)
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    WsReplySum base = ws_reply_sum_none(), total = ws_reply_sum_none();
-#pragma unroll
-    for (u32 k = 0; k < REPLY_T / 64; ++k) {
-        const WsReplySum w = wsum[k];
-        if (k < wv) base = ws_reply_comb_seg(base, w);
-        total = ws_reply_comb_seg(total, w);
-    }
-    *excl = ws_reply_comb_seg(base, e);
-    return total;
-}
-
-// exclusive scan of v over the block's REPLY_T threads; the block's sum is returned
-template <typename T>
-__device__ __forceinline__ T reply_block_sum(T v, T* wsum, T* excl) {
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = (T)shfl_up64((u64)inc, d);
-        if (lane >= (u32)d) inc += o;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    T base = 0, total = 0;
-#pragma unroll
-    for (u32 k = 0; k < REPLY_T / 64; ++k) {
-        if (k < wv) base += wsum[k];
-        total += wsum[k];
-    }
-    *excl = base + inc - v;
-    return total;
-}
-
-__device__ __forceinline__ u32 reply_count(const WebsocketSegResult_t* res, u32 s, u32 max_frames, u64* consumed) {
-    const u32x4 r = *gptr<u32x4>(res + s);
-    *consumed = (u64)r.x | (u64)r.y << 32;
-    return r.z < max_frames ? r.z : max_frames;
-}
+struct ReplyOps {                        // ws_scan.h's view of ws_reply.h's run summary
+    typedef WsReplySum Sum;
+    static constexpr u32 HEAD = WS_REPLY_S_HEAD;
+    static __device__ __forceinline__ Sum none() { return ws_reply_sum_none(); }
+    static __device__ __forceinline__ Sum comb(const Sum& a, const Sum& b) { return ws_reply_comb(a, b); }
+    static __device__ __forceinline__ Sum comb_seg(const Sum& a, const Sum& b) { return ws_reply_comb_seg(a, b); }
+};
 
 __global__ __launch_bounds__(REPLY_T) void ws_reply_plan(const WebsocketSegResult_t* res, u32 nseg, u32 max_frames,
                                                          u32* loff, u32* blocksum) {
     __shared__ u32 wsum[REPLY_T / 64];
     const u32 s = blockIdx.x * REPLY_T + threadIdx.x;
     u64 consumed;
-    const u32 n = s < nseg ? reply_count(res, s, max_frames, &consumed) : 0u;
+    const u32 n = s < nseg ? ws_seg_count(res, s, max_frames, &consumed) : 0u;
     u32 excl;
-    const u32 total = reply_block_sum<u32>(n, wsum, &excl);
+    const u32 total = ws_block_sum<REPLY_T>(n, wsum, &excl);
     loff[s] = excl;                                    // (loff is padded to whole blocks)
     if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
 }
@@ -149,54 +61,12 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_plan(const WebsocketSegResul
 template <typename T>
 __global__ __launch_bounds__(1024) void ws_reply_scan(T* bo, u32 nb, T* total_out) {
     __shared__ T part[1024];
-    const u32 t = threadIdx.x, per = (nb + 1023) / 1024;
-    const u32 lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
-    T sum = 0;
-    for (u32 k = lo; k < hi; ++k) sum += bo[k];
-    part[t] = sum;
-    __syncthreads();
-    for (u32 d = 1; d < 1024; d <<= 1) {
-        const T o = t >= d ? part[t - d] : (T)0;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    T run = part[t] - sum;
-    for (u32 k = lo; k < hi; ++k) {
-        const T v = bo[k];
-        bo[k] = run;
-        run += v;
-    }
-    if (t == 1023) {
-        bo[nb] = part[1023];
-        total_out[0] = part[1023];
-    }
+    ws_offsets_scan(bo, nb, total_out, part);
 }
 
-// the list position of segment s's first frame (s < nseg)
-__device__ __forceinline__ u32 reply_start(const u32* bo, const u32* loff, u32 s) { return bo[s / REPLY_T] + loff[s]; }
-
-// the largest s in [0, nseg) with reply_start(s) <= f (f wave-uniform and below the total: that
-// segment is not empty), by the whole wave
-__device__ __forceinline__ u32 reply_search(const u32* bo, const u32* loff, u32 nseg, u32 f, u32 lane) {
-    u32 lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const u32 step = (hi - lo + 63) / 64;
-        const u64 idx = (u64)lo + (u64)lane * step;
-        const bool le = idx < hi && reply_start(bo, loff, (u32)idx) <= f;
-        const u32 cnt = (u32)__popcll(__ballot(le));   // >= 1: lane 0 probes lo
-        lo += (cnt - 1) * step;
-        hi = hi < lo + step ? hi : lo + step;
-    }
-    return lo;
-}
-
-// This thread's frame of tile t: its segment and index, the descriptor's fields, whether it is
-// consumed, and its summary (with HEAD on a segment's first frame).
+// This thread's frame of tile t (ws_frame_mine) and its summary (with HEAD on a segment's first frame).
 struct ReplyMine {
-    bool valid, consumed;
-    u32 s, k, n, type, fin, masked;
-    u64 data_off, datalen;
+    WsFrameMine f;
     WsReplySum sum;
 };
 
@@ -204,42 +74,14 @@ __device__ __forceinline__ ReplyMine reply_mine(u32 t, u32 total, const u32* bo,
                                                 const u64* seg_off, const WebsocketFrameDesc_t* desc,
                                                 const WebsocketSegResult_t* res, const WebsocketProtoResult_t* pres,
                                                 u32 keyed) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 f0 = t * REPLY_T + (threadIdx.x & ~63u), f = f0 + lane;   // (total <= 2^30: no wrap)
     ReplyMine m;
-    m.valid = f < total;
-    m.consumed = false;
-    m.s = m.k = m.n = m.type = m.fin = m.masked = 0;
-    m.data_off = m.datalen = 0;
+    m.f = ws_frame_mine<REPLY_T>(t, total, bo, loff, nseg, max_frames, seg_off, desc, res);
     m.sum = ws_reply_sum_none();
-    if (f0 >= total) return m;                         // (wave-uniform)
-    const u32 f1 = f0 + 63 < total ? f0 + 63 : total - 1;
-    const u32 s0 = reply_search(bo, loff, nseg, f0, lane);
-    const u32 s1 = f1 == f0 ? s0 : reply_search(bo, loff, nseg, f1, lane);
-    if (!m.valid) return m;
-    u32 lo = s0, hi = s1 + 1;
-    while (hi - lo > 1) {
-        const u32 mid = lo + (hi - lo) / 2;
-        if (reply_start(bo, loff, mid) <= f) lo = mid;
-        else hi = mid;
+    if (m.f.consumed) {
+        const u32 first_bad = pres ? *gptr<u32>(&pres[m.f.s].first_bad) : WS_REPLY_NONE;
+        m.sum = ws_reply_sum_frame(m.f.d.type, m.f.d.fin, m.f.d.datalen, m.f.k, (u32)(m.f.k < first_bad), keyed);
     }
-    m.s = lo;
-    m.k = f - reply_start(bo, loff, lo);
-    u64 consumed;
-    m.n = reply_count(res, m.s, max_frames, &consumed);
-    const gu32x4* const d = gptr<u32x4>(desc + ((u64)m.s * max_frames + m.k));
-    const u32x4 d0 = d[0], d1 = d[1];
-    const u64 frame_off = (u64)d0.x | (u64)d0.y << 32;
-    m.data_off = (u64)d0.z | (u64)d0.w << 32;
-    m.datalen = (u64)d1.x | (u64)d1.y << 32;
-    const int ret = (int)d1.z;
-    m.fin = d1.w & 0xFFu;
-    m.type = (d1.w >> 8) & 0xFFu;
-    m.masked = (d1.w >> 16) & 0xFFu;
-    m.consumed = ret > 0 && frame_off + (u64)ret <= seg_off[m.s] + consumed;
-    const u32 first_bad = pres ? *gptr<u32>(&pres[m.s].first_bad) : WS_REPLY_NONE;
-    if (m.consumed) m.sum = ws_reply_sum_frame(m.type, m.fin, m.datalen, m.k, (u32)(m.k < first_bad), keyed);
-    if (m.k == 0) m.sum.bits |= WS_REPLY_S_HEAD;
+    if (m.f.valid && m.f.k == 0) m.sum.bits |= WS_REPLY_S_HEAD;
     return m;
 }
 
@@ -253,9 +95,9 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_sums(const u64* seg_off, con
     for (u32 t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const ReplyMine m = reply_mine(t, total, bo, loff, nseg, max_frames, seg_off, desc, res, pres, keyed);
         WsReplySum excl;
-        const WsReplySum all = reply_block_scan(m.sum, wsum, &excl);
-        if (threadIdx.x == 0) reply_st(agg + t, all);
-        if (m.valid && m.k == m.n - 1) reply_st(tail + m.s, ws_reply_comb_seg(excl, m.sum));
+        const WsReplySum all = ws_seg_block_scan<REPLY_T, ReplyOps>(m.sum, wsum, &excl);
+        if (threadIdx.x == 0) ws_st(agg + t, all);
+        if (m.f.valid && m.f.k == m.f.n - 1) ws_st(tail + m.f.s, ws_reply_comb_seg(excl, m.sum));
     }
 }
 
@@ -263,25 +105,7 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_sums(const u64* seg_off, con
 // brings along from the tiles before)
 __global__ __launch_bounds__(1024) void ws_reply_combine(WsReplySum* agg, const u32* head) {
     __shared__ WsReplySum part[1024];
-    const u32 nt = (head[0] + REPLY_T - 1) / REPLY_T;
-    const u32 t = threadIdx.x, per = (nt + 1023) / 1024;
-    const u32 lo = t * per < nt ? t * per : nt, hi = lo + per < nt ? lo + per : nt;
-    WsReplySum sum = ws_reply_sum_none();
-    for (u32 k = lo; k < hi; ++k) sum = ws_reply_comb_seg(sum, reply_ld(agg + k));
-    part[t] = sum;
-    __syncthreads();
-    for (u32 d = 1; d < 1024; d <<= 1) {
-        const WsReplySum o = t >= d ? part[t - d] : ws_reply_sum_none();
-        __syncthreads();
-        part[t] = ws_reply_comb_seg(o, part[t]);
-        __syncthreads();
-    }
-    WsReplySum run = t ? part[t - 1] : ws_reply_sum_none();
-    for (u32 k = lo; k < hi; ++k) {
-        const WsReplySum v = reply_ld(agg + k);
-        reply_st(agg + k, run);
-        run = ws_reply_comb_seg(run, v);
-    }
+    ws_seg_combine<ReplyOps>(agg, (head[0] + REPLY_T - 1) / REPLY_T, part);
 }
 
 __global__ __launch_bounds__(REPLY_T) void ws_reply_segs(const unsigned char* buf, const WebsocketFrameDesc_t* desc,
@@ -296,14 +120,9 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_segs(const unsigned char* bu
     WsReplyRec r = {0ull, 0ull, 0u, WS_REPLY_NONE, 0u, 0u};
     if (s < nseg) {
         u64 consumed;
-        const u32 n = reply_count(res, s, max_frames, &consumed);
-        WsReplySum all = ws_reply_sum_none();
-        if (n) {
-            // the segment's frames inside its last tile, behind those of the tiles before
-            const u32 start = reply_start(bo, loff, s), tl = (start + n - 1) / REPLY_T;
-            all = reply_ld(tail + s);
-            if (start < tl * REPLY_T) all = ws_reply_comb(reply_ld(agg + tl), all);
-        }
+        const u32 n = ws_seg_count(res, s, max_frames, &consumed);
+        const WsReplySum all =
+            n ? ws_seg_fold<REPLY_T, ReplyOps>(tail + s, agg, ws_list_start<REPLY_T>(bo, loff, s), n) : ws_reply_sum_none();
         u32 first_bad = WS_REPLY_NONE, proto_status = 0;
         if (pres) {
             const u32x4 p = *gptr<u32x4>(pres + s);
@@ -316,11 +135,8 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_segs(const unsigned char* bu
         if (kind == WEBSOCKET_REPLY_CLOSE_PROTOCOL) status = proto_status;
         else if (kind == WEBSOCKET_REPLY_CLOSE_CALLER) status = fs;
         else if (kind == WEBSOCKET_REPLY_CLOSE_ECHO && !(st & WEBSOCKET_REPLY_ST_CLOSE_SENT)) {
-            const gu32x4* const d = gptr<u32x4>(desc + ((u64)s * max_frames + all.close));
-            const u32x4 d0 = d[0], d1 = d[1];
-            const u64 data_off = (u64)d0.z | (u64)d0.w << 32, datalen = (u64)d1.x | (u64)d1.y << 32;
-            const u32 masked = (d1.w >> 16) & 0xFFu;
-            if (datalen >= 2) status = ws_reply_echo_status(buf + data_off, (flags & WEBSOCKET_REPLY_WIRE_MASKED) && masked);
+            const WsDesc d = ws_desc_ld(desc + ((u64)s * max_frames + all.close));
+            if (d.datalen >= 2) status = ws_reply_echo_status(buf + d.data_off, (flags & WEBSOCKET_REPLY_WIRE_MASKED) && d.masked);
             else body = 0;
         }
         const WsReplySeg g = ws_reply_seg(all, first_bad, st, flags, keyed, kind, status, body);
@@ -335,9 +151,9 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_segs(const unsigned char* bu
         r.close = g.close_len ? g.close_len | g.close_status << 16 : 0u;
     }
     u64 excl;
-    const u64 total = reply_block_sum<u64>(bytes, wsum, &excl);
+    const u64 total = ws_block_sum<REPLY_T>(bytes, wsum, &excl);
     r.loc_off = excl;
-    if (s < nseg) rec_st(rec + s, r);
+    if (s < nseg) ws_st(rec + s, r);
     if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
 }
 
@@ -352,7 +168,7 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_emit(const unsigned char* bu
     // the segments: d_tx_off[s] and the CLOSE
     for (u64 s64 = (u64)blockIdx.x * REPLY_T + threadIdx.x; s64 < nseg; s64 += (u64)gridDim.x * REPLY_T) {
         const u32 s = (u32)s64;
-        const WsReplyRec r = rec_ld(rec + s);
+        const WsReplyRec r = ws_ld(rec + s);
         const u64 base = bo64[s / REPLY_T] + r.loc_off;
         tx_off[s] = base;
         if (r.close) {
@@ -363,35 +179,33 @@ __global__ __launch_bounds__(REPLY_T) void ws_reply_emit(const unsigned char* bu
     // the frames: every answered ping's PONG
     const u32 total = head[0], ntiles = (total + REPLY_T - 1) / REPLY_T;
     for (u32 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const ReplyMine m = reply_mine(t, total, bo, loff, nseg, max_frames, seg_off, desc, res, pres, keyed);
-        WsReplySum before;
-        reply_block_scan(m.sum, wsum, &before);
+        const ReplyMine rm = reply_mine(t, total, bo, loff, nseg, max_frames, seg_off, desc, res, pres, keyed);
+        const WsFrameMine& m = rm.f;
+        WsReplySum excl;
+        ws_seg_block_scan<REPLY_T, ReplyOps>(rm.sum, wsum, &excl);
         bool answer = false;
         u64 off = 0;
         u32 key = 0;
-        if (m.valid && m.consumed) {
-            const WsReplyRec r = rec_ld(rec + m.s);
+        if (m.consumed) {
+            const WsReplyRec r = ws_ld(rec + m.s);
             WsReplySeg g = {};
             g.end = r.end;
             g.only = r.only;
-            answer = ws_reply_answers(g, flags, m.k, m.type, m.fin, m.datalen) != 0u;
+            answer = ws_reply_answers(g, flags, m.k, m.d.type, m.d.fin, m.d.datalen) != 0u;
             if (answer) {
-                // the frames of this segment before this one: none (its first frame), those of this
-                // tile (the segment starts in it), or those with the tiles before
-                if (m.k == 0) before = ws_reply_sum_none();
-                else if (!(before.bits & WS_REPLY_S_HEAD)) before = ws_reply_comb(reply_ld(agg + t), before);
+                const WsReplySum before = ws_seg_before<ReplyOps>(excl, m.k == 0, agg + t);
                 off = bo64[m.s / REPLY_T] + r.loc_off + ((flags & WEBSOCKET_REPLY_LAST_PING_ONLY) ? 0ull : before.bytes);
                 if (keyed) key = keys[(u64)m.s * (max_frames + 1ull) + m.k];
             }
         }
         // the wave copies its PONGs one after the other
-        const u32 wm = (flags & WEBSOCKET_REPLY_WIRE_MASKED) && m.masked;
+        const u32 wm = (flags & WEBSOCKET_REPLY_WIRE_MASKED) && m.d.masked;
         u64 todo = __ballot(answer);
         while (todo) {
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1;
-            const u64 o = shfl64(off, src), doff = shfl64(m.data_off, src);
-            const u32 len = (u32)__shfl((int)(u32)m.datalen, src);
+            const u64 o = ws_shfl(off, src), doff = ws_shfl(m.d.data_off, src);
+            const u32 len = (u32)__shfl((int)(u32)m.d.datalen, src);
             const WsReplyFrame f = ws_reply_pong(buf, doff, len, (u32)__shfl((int)wm, src), keyed, (u32)__shfl((int)key, src));
             const u32 nbytes = ws_reply_frame_len(len, keyed);
             for (u32 j = lane; j < nbytes; j += 64)

@@ -6,7 +6,8 @@
 // message by division by the frame stride.
 //
 // The message slots of all connections, s * max_msgs + i, form one list; a tile is 256 consecutive
-// slots of it, one per thread (the tile and scan shape of ws_reply.hip, no atomics).
+// slots of it, one per thread (the tile scan, the carries and the offsets scan are ws_scan.h's, one
+// definition; no atomics).
 //   sums     a fixed grid over the tiles: every slot's summary (its entry validated, its wire
 //            length and frame count in closed form), the block's segmented scan; the tile's
 //            summary, and for a connection's last slot the fold of its slots inside this tile;
@@ -32,7 +33,7 @@
 // Every output is written with plain vector stores.
 #include <stdio.h>
 
-#include "ws_common.h"
+#include "ws_scan.h"
 #include "ws_send.h"
 
 #define SEND_T 256                       // threads per block: slots per tile, connections per segs block
@@ -48,97 +49,15 @@ static_assert(sizeof(WsSendSum) == 32 && sizeof(WsSendRec) == 48 && sizeof(Webso
 
 typedef u32x4 __attribute__((aligned(1))) u32x4u;
 
-__device__ __forceinline__ u64 pack64(u32 lo, u32 hi) { return (u64)lo | (u64)hi << 32; }
+struct SendOps {                         // ws_scan.h's view of ws_send.h's slot summary
+    typedef WsSendSum Sum;
+    static constexpr u32 HEAD = WS_SEND_S_HEAD;
+    static __device__ __forceinline__ Sum none() { return ws_send_sum_none(); }
+    static __device__ __forceinline__ Sum comb(const Sum& a, const Sum& b) { return ws_send_comb(a, b); }
+    static __device__ __forceinline__ Sum comb_seg(const Sum& a, const Sum& b) { return ws_send_comb_seg(a, b); }
+};
 
-__device__ __forceinline__ WsSendSum sum_ld(const WsSendSum* p) {
-    const gu32x4* const g = gptr<u32x4>(p);
-    const u32x4 a = g[0], b = g[1];
-    return WsSendSum{a.x, a.y, a.z, a.w, pack64(b.x, b.y), pack64(b.z, b.w)};
-}
-__device__ __forceinline__ void sum_st(WsSendSum* p, const WsSendSum& s) {
-    u32x4 a, b;
-    a.x = s.bits; a.y = s.first_bad; a.z = s.status; a.w = s.nmsg;
-    b.x = (u32)s.bytes; b.y = (u32)(s.bytes >> 32); b.z = (u32)s.frames; b.w = (u32)(s.frames >> 32);
-    gu32x4* const g = gptr<u32x4>(p);
-    g[0] = a;
-    g[1] = b;
-}
-__device__ __forceinline__ WsSendRec rec_ld(const WsSendRec* p) {
-    const gu32x4* const g = gptr<u32x4>(p);
-    const u32x4 a = g[0], b = g[1], c = g[2];
-    return WsSendRec{pack64(a.x, a.y), pack64(a.z, a.w), pack64(b.x, b.y), pack64(b.z, b.w), c.x, c.y, c.z, c.w};
-}
-__device__ __forceinline__ void rec_st(WsSendRec* p, const WsSendRec& r) {
-    u32x4 a, b, c;
-    a.x = (u32)r.tx_off; a.y = (u32)(r.tx_off >> 32); a.z = (u32)r.src_off; a.w = (u32)(r.src_off >> 32);
-    b.x = (u32)r.len; b.y = (u32)(r.len >> 32); b.z = (u32)r.wire; b.w = (u32)(r.wire >> 32);
-    c.x = r.shard; c.y = r.key; c.z = r.type; c.w = r.role;
-    gu32x4* const g = gptr<u32x4>(p);
-    g[0] = a;
-    g[1] = b;
-    g[2] = c;
-}
 __device__ __forceinline__ u64 rec_tx_off(const WsSendRec* p) { return *gptr<u64>(p); }
-
-__device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
-    return (u64)(u32)__shfl_up((int)(u32)v, d) | (u64)(u32)__shfl_up((int)(u32)(v >> 32), d) << 32;
-}
-__device__ __forceinline__ WsSendSum sum_shfl_up(const WsSendSum& s, int d) {
-    WsSendSum r;
-    r.bits = (u32)__shfl_up((int)s.bits, d);
-    r.first_bad = (u32)__shfl_up((int)s.first_bad, d);
-    r.status = (u32)__shfl_up((int)s.status, d);
-    r.nmsg = (u32)__shfl_up((int)s.nmsg, d);
-    r.bytes = shfl_up64(s.bytes, d);
-    r.frames = shfl_up64(s.frames, d);
-    return r;
-}
-
-// Segmented scan (ws_send_comb_seg) over the block's SEND_T values in thread order: *excl takes
-// the fold of the values before this thread, the fold of all of them is returned.
-__device__ __forceinline__ WsSendSum send_block_scan(WsSendSum v, WsSendSum* wsum, WsSendSum* excl) {
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const WsSendSum o = sum_shfl_up(v, d);
-        if (lane >= (u32)d) v = ws_send_comb_seg(o, v);
-    }
-    WsSendSum e = sum_shfl_up(v, 1);
-    if (lane == 0) e = ws_send_sum_none();
-    __syncthreads();                                   // (the previous tile's readers of wsum are done)
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    WsSendSum base = ws_send_sum_none(), total = ws_send_sum_none();
-#pragma unroll
-    for (u32 k = 0; k < SEND_T / 64; ++k) {
-        const WsSendSum w = wsum[k];
-        if (k < wv) base = ws_send_comb_seg(base, w);
-        total = ws_send_comb_seg(total, w);
-    }
-    *excl = ws_send_comb_seg(base, e);
-    return total;
-}
-
-// exclusive scan of v over the block's SEND_T threads; the block's sum is returned
-__device__ __forceinline__ u64 send_block_sum(u64 v, u64* wsum, u64* excl) {
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 o = shfl_up64(inc, d);
-        if (lane >= (u32)d) inc += o;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    u64 base = 0, total = 0;
-#pragma unroll
-    for (u32 k = 0; k < SEND_T / 64; ++k) {
-        if (k < wv) base += wsum[k];
-        total += wsum[k];
-    }
-    *excl = base + inc - v;
-    return total;
-}
 
 // This thread's slot of tile t: its connection and index, the connection's count, fragment size
 // and shard, the entry, and its summary (with HEAD on a connection's first slot).
@@ -187,9 +106,9 @@ __global__ __launch_bounds__(SEND_T) void ws_send_sums(const WebsocketSendMsg_t*
     for (u32 t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const SendMine m = send_mine(t, nslots, max_msgs, src_len, msg, nmsg, frag, keys);
         WsSendSum excl;
-        const WsSendSum all = send_block_scan(m.sum, wsum, &excl);
-        if (threadIdx.x == 0) sum_st(agg + t, all);
-        if (m.valid && m.i == max_msgs - 1) sum_st(tail + m.s, ws_send_comb_seg(excl, m.sum));
+        const WsSendSum all = ws_seg_block_scan<SEND_T, SendOps>(m.sum, wsum, &excl);
+        if (threadIdx.x == 0) ws_st(agg + t, all);
+        if (m.valid && m.i == max_msgs - 1) ws_st(tail + m.s, ws_send_comb_seg(excl, m.sum));
     }
 }
 
@@ -197,24 +116,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_sums(const WebsocketSendMsg_t*
 // brings along from the tiles before)
 __global__ __launch_bounds__(1024) void ws_send_combine(WsSendSum* agg, u32 nt) {
     __shared__ WsSendSum part[1024];
-    const u32 t = threadIdx.x, per = (nt + 1023) / 1024;
-    const u32 lo = t * per < nt ? t * per : nt, hi = lo + per < nt ? lo + per : nt;
-    WsSendSum sum = ws_send_sum_none();
-    for (u32 k = lo; k < hi; ++k) sum = ws_send_comb_seg(sum, sum_ld(agg + k));
-    part[t] = sum;
-    __syncthreads();
-    for (u32 d = 1; d < 1024; d <<= 1) {
-        const WsSendSum o = t >= d ? part[t - d] : ws_send_sum_none();
-        __syncthreads();
-        part[t] = ws_send_comb_seg(o, part[t]);
-        __syncthreads();
-    }
-    WsSendSum run = t ? part[t - 1] : ws_send_sum_none();
-    for (u32 k = lo; k < hi; ++k) {
-        const WsSendSum v = sum_ld(agg + k);
-        sum_st(agg + k, run);
-        run = ws_send_comb_seg(run, v);
-    }
+    ws_seg_combine<SendOps>(agg, nt, part);
 }
 
 __global__ __launch_bounds__(SEND_T) void ws_send_segs(u32 nseg, u32 max_msgs, const WsSendSum* agg, const WsSendSum* tail,
@@ -223,22 +125,12 @@ __global__ __launch_bounds__(SEND_T) void ws_send_segs(u32 nseg, u32 max_msgs, c
     const u32 s = blockIdx.x * SEND_T + threadIdx.x;
     u64 bytes = 0;
     if (s < nseg) {
-        // the connection's slots inside its last tile, behind those of the tiles before
-        const u64 first = (u64)s * max_msgs;
-        const u32 tl = (u32)((first + max_msgs - 1) / SEND_T);
-        WsSendSum all = sum_ld(tail + s);
-        if (first < (u64)tl * SEND_T) all = ws_send_comb(sum_ld(agg + tl), all);
-        const WebsocketSendResult_t r = ws_send_result(all);
+        const WebsocketSendResult_t r = ws_send_result(ws_seg_fold<SEND_T, SendOps>(tail + s, agg, (u64)s * max_msgs, max_msgs));
         bytes = r.tx_len;
-        u32x4 a, b;
-        a.x = (u32)r.tx_len; a.y = (u32)(r.tx_len >> 32); a.z = (u32)r.n_frames; a.w = (u32)(r.n_frames >> 32);
-        b.x = r.n_msgs; b.y = r.status; b.z = r.first_bad; b.w = 0u;
-        gu32x4* const g = gptr<u32x4>(out + s);
-        g[0] = a;
-        g[1] = b;
+        ws_st(out + s, r);
     }
     u64 excl;
-    const u64 total = send_block_sum(bytes, wsum, &excl);
+    const u64 total = ws_block_sum<SEND_T>(bytes, wsum, &excl);
     loc[s] = excl;                                     // (loc is padded to whole blocks)
     if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
 }
@@ -246,28 +138,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_segs(u32 nseg, u32 max_msgs, c
 // exclusive scan of the nb block sums in place; bo[nb] and *total_out take the total
 __global__ __launch_bounds__(1024) void ws_send_offs(u64* bo, u32 nb, u64* total_out) {
     __shared__ u64 part[1024];
-    const u32 t = threadIdx.x, per = (nb + 1023) / 1024;
-    const u32 lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
-    u64 sum = 0;
-    for (u32 k = lo; k < hi; ++k) sum += bo[k];
-    part[t] = sum;
-    __syncthreads();
-    for (u32 d = 1; d < 1024; d <<= 1) {
-        const u64 o = t >= d ? part[t - d] : 0ull;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    u64 run = part[t] - sum;
-    for (u32 k = lo; k < hi; ++k) {
-        const u64 v = bo[k];
-        bo[k] = run;
-        run += v;
-    }
-    if (t == 1023) {
-        bo[nb] = part[1023];
-        total_out[0] = part[1023];
-    }
+    ws_offsets_scan(bo, nb, total_out, part);
 }
 
 __global__ __launch_bounds__(SEND_T) void ws_send_recs(const WebsocketSendMsg_t* msg, const u32* nmsg, const u32* frag,
@@ -280,13 +151,10 @@ __global__ __launch_bounds__(SEND_T) void ws_send_recs(const WebsocketSendMsg_t*
     const u64 np = ws_send_pieces(limit, lead);
     for (u32 t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const SendMine m = send_mine(t, nslots, max_msgs, src_len, msg, nmsg, frag, keys);
-        WsSendSum before;
-        send_block_scan(m.sum, wsum, &before);
+        WsSendSum excl;
+        ws_seg_block_scan<SEND_T, SendOps>(m.sum, wsum, &excl);
         if (!m.valid) continue;
-        // the slots of this connection before this one: none (its first slot), those of this tile
-        // (the connection starts in it), or those with the tiles before
-        if (m.i == 0) before = ws_send_sum_none();
-        else if (!(before.bits & WS_SEND_S_HEAD)) before = ws_send_comb(sum_ld(agg + t), before);
+        const WsSendSum before = ws_seg_before<SendOps>(excl, m.i == 0, agg + t);
         const bool ok = *gptr<u32>(&res[m.s].status) == WEBSOCKET_SEND_OK;
         const u64 base = bo64[m.s / SEND_T] + loc[m.s];
         WsSendRec r;
@@ -298,7 +166,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_recs(const WebsocketSendMsg_t*
         r.key = m.key;
         r.type = m.m.type;
         r.role = keys ? 1u : 0u;
-        rec_st(rec + m.q, r);
+        ws_st(rec + m.q, r);
         if (m.i == 0) tx_off[m.s] = base;
         if (msg_tx_off && m.live) msg_tx_off[m.q] = r.tx_off;
         if (r.wire && r.tx_off < limit) {
@@ -371,7 +239,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_emit(const unsigned char* src,
             }
         }
         u32 j = lo + a;
-        WsSendRec r = rec_ld(rec + j);
+        WsSendRec r = ws_ld(rec + j);
         u64 k;
         u32 fk;
         if (y >= lead && y + 16 <= limit + lead && send_interior(r, xs - r.tx_off, &k, &fk)) {
@@ -391,7 +259,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_emit(const unsigned char* src,
         while (i < 16) {
             const u64 x = y + i - lead;
             if (x >= limit) break;
-            while (x >= r.tx_off + r.wire && j + 1 < nslots) r = rec_ld(rec + ++j);   // (x < total: a record holds it)
+            while (x >= r.tx_off + r.wire && j + 1 < nslots) r = ws_ld(rec + ++j);   // (x < total: a record holds it)
             if (x - r.tx_off >= r.wire) break;
             const WsSendLoc f = ws_send_locate(r, x - r.tx_off);
             const u32 hx = f.hl + (r.role ? 4u : 0u);
@@ -456,8 +324,8 @@ __global__ __launch_bounds__(SEND_T) void ws_send_list(const WebsocketFrameDesc_
     }
     const bool send = type != WEBSOCKET_SEND_SKIP;
     gu64* const o = gptr<u64>(out + q);
-    o[0] = send ? pack64(a.x, a.y) : 0ull;
-    o[1] = send ? pack64(a.z, a.w) : 0ull;
+    o[0] = send ? (u64)a.x | (u64)a.y << 32 : 0ull;
+    o[1] = send ? (u64)a.z | (u64)a.w << 32 : 0ull;
     o[2] = (u64)type;
 }
 

@@ -2,7 +2,8 @@
 // validation of reassembled text messages and CLOSE reasons, for gfx950. The byte rule, the
 // unfinished tail and the state word are ws_utf8.h's (one definition, host-tested).
 //
-// Work is divided by bytes. The host knows no sizes, so the plan is made on the device:
+// Work is divided by bytes. The host knows no sizes, so the plan is made on the device (the block
+// sum, the offsets scan and the wave search are ws_scan.h's, one definition):
 //   plan    one thread per message slot: class (text / CLOSE reason / not checked), the body's
 //           tile count (tiles of UTF8_TILE bytes of the 16-B aligned address space that holds the
 //           body), the unfinished tail from the body's last three bytes, the exclusive scan of
@@ -21,7 +22,7 @@
 //           writes the segment's state word.
 // Every output is written with plain stores or vector atomics.
 #include "../../include/wsframe_amd_text.h"
-#include "ws_common.h"
+#include "ws_scan.h"
 #include "ws_utf8.h"
 
 #define UTF8_T 256                       // threads per block, and slots per plan block
@@ -112,64 +113,16 @@ __global__ __launch_bounds__(UTF8_T) void ws_utf8_plan(const unsigned char* out,
         info[slot] = inf;
     }
     // exclusive scan of the block's tile counts
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u32 inc = tiles;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 o = (u32)__shfl_up((int)inc, d);
-        if (lane >= (u32)d) inc += o;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    u32 base = 0, total = 0;
-#pragma unroll
-    for (u32 k = 0; k < UTF8_T / 64; ++k) {
-        if (k < wv) base += wsum[k];
-        total += wsum[k];
-    }
-    loff[slot] = base + inc - tiles;                  // (loff and info are padded to whole blocks)
+    u32 excl;
+    const u32 total = ws_block_sum<UTF8_T>(tiles, wsum, &excl);
+    loff[slot] = excl;                                // (loff and info are padded to whole blocks)
     if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
 }
 
 // exclusive scan of the nb block sums in place; bo[nb] and head[0] take the total
 __global__ __launch_bounds__(1024) void ws_utf8_scan(u32* bo, u32 nb, u32* head) {
     __shared__ u32 part[1024];
-    const u32 t = threadIdx.x, per = (nb + 1023) / 1024;
-    const u32 lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
-    u32 sum = 0;
-    for (u32 k = lo; k < hi; ++k) sum += bo[k];
-    part[t] = sum;
-    __syncthreads();
-    for (u32 d = 1; d < 1024; d <<= 1) {
-        const u32 o = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    u32 run = part[t] - sum;
-    for (u32 k = lo; k < hi; ++k) {
-        const u32 v = bo[k];
-        bo[k] = run;
-        run += v;
-    }
-    if (t == 1023) {
-        bo[nb] = part[1023];
-        head[0] = part[1023];
-    }
-}
-
-// the largest idx in [0, n) with arr[idx] <= t (arr non-decreasing, arr[0] <= t), by the whole wave
-__device__ __forceinline__ u32 utf8_search(const u32* arr, u32 n, u32 t, u32 lane) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u32 step = (hi - lo + 63) / 64;
-        const u64 idx = (u64)lo + (u64)lane * step;
-        const bool le = idx < hi && arr[idx] <= t;
-        const u32 cnt = (u32)__popcll(__ballot(le));   // >= 1: lane 0 probes lo
-        lo += (cnt - 1) * step;
-        hi = hi < lo + step ? hi : lo + step;
-    }
-    return lo;
+    ws_offsets_scan(bo, nb, head, part);
 }
 
 __global__ __launch_bounds__(UTF8_T) void ws_utf8_tiles(const unsigned char* out, const WebsocketFrameDesc_t* desc,
@@ -187,9 +140,11 @@ __global__ __launch_bounds__(UTF8_T) void ws_utf8_tiles(const unsigned char* out
     u32 ph = 0, carry3 = 0;
     for (u64 t = t0; t < t1; ++t) {
         if (t >= slot_hi) {
-            const u32 b = utf8_search(bo, nb, (u32)t, lane);
+            // the last block, then the last slot of it, that starts at or before tile t
+            const u32 b = ws_wave_search([&](u32 i) { return bo[i]; }, nb, (u32)t, lane);
             const u32 bbase = bo[b];
-            const u32 j = utf8_search(loff + (u64)b * UTF8_T, UTF8_T, (u32)t - bbase, lane);
+            const u32* const lb = loff + (u64)b * UTF8_T;
+            const u32 j = ws_wave_search([&](u32 i) { return lb[i]; }, UTF8_T, (u32)t - bbase, lane);
             slot = (u64)b * UTF8_T + j;
             const Utf8Body bd = utf8_body(out, desc, msg[slot], state, (u32)(slot / max_frames), max_frames);
             slot_lo = (u64)bbase + loff[slot];
