@@ -2,7 +2,8 @@
 workspace per stream), calls issued back to back with no host synchronisation between
 them, and from two host threads at once. Every batch vs the oracle, bit-exact; then more
 streams than the per-device workspace table holds (the least recently used slot is
-taken after a device synchronize)."""
+taken after a device synchronize).
+The other device entry points under the same conditions: tests/test_gpu_concurrent_calls.py."""
 import threading
 
 import numpy as np
