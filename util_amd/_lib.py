@@ -79,7 +79,13 @@ CLI_LIB_PATH = os.path.join(HERE, "libwsframe_amd_cli.so")
 CLI_EXPORTS = ["websocketframeBatchClientRequestDevice", "websocketframeBatchClientVerifyDevice",
                "websocketframeClientRequestHost", "websocketframeClientVerifyHost"]
 _cli = None
-_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply, send and cli libraries keep their own copies
+# libwsframe_amd_deflate.so: everything libwsframe_amd_cli.so exports plus the WSFRAME_AMD_DEFLATE_EXPORT
+# entry points (include/wsframe_amd_deflate.h)
+DEFLATE_LIB_PATH = os.path.join(HERE, "libwsframe_amd_deflate.so")
+DEFLATE_EXPORTS = ["websocketframeBatchInflateDevice", "websocketframeBatchInflateListFromMessagesDevice",
+                   "websocketframeInflateHost"]
+_deflate = None
+_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply, send, cli and deflate libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -191,6 +197,8 @@ def set_option(name, value):
             _send.websocketframeGpuSetOption(name.encode(), int(value))
         if _cli is not None:
             _cli.websocketframeGpuSetOption(name.encode(), int(value))
+        if _deflate is not None:
+            _deflate.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -429,6 +437,36 @@ def load_cli_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _cli = lib
+    return lib
+
+
+def load_deflate_lib():
+    """libwsframe_amd_deflate.so: the permessage-deflate receive side (websocketframeBatchInflateDevice,
+    websocketframeBatchInflateListFromMessagesDevice, websocketframeInflateHost) next to the whole C
+    ABI of libwsframe_amd_cli.so. A library of its own state, as load_cli_lib(): the options set so
+    far are applied when it loads and forwarded afterwards."""
+    global _deflate
+    if _deflate is not None:
+        return _deflate
+    load_lib()
+    if not os.path.exists(DEFLATE_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_deflate.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(DEFLATE_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchInflateDevice.restype = i32
+    lib.websocketframeBatchInflateDevice.argtypes = [vp, u64, vp, vp, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]
+    lib.websocketframeBatchInflateListFromMessagesDevice.restype = i32
+    lib.websocketframeBatchInflateListFromMessagesDevice.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    lib.websocketframeInflateHost.restype = C.c_longlong
+    lib.websocketframeInflateHost.argtypes = [vp, u64, vp, u32, u64, u32, vp, u64, vp, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _deflate = lib
     return lib
 
 

@@ -76,6 +76,16 @@ SEND_RES_DTYPE = np.dtype([("tx_len", "<u8"), ("n_frames", "<u8"), ("n_msgs", "<
 assert SEND_RES_DTYPE.itemsize == 32
 SEND_SKIP = SEND_NONE = SEND_FRAG_DEFAULT = 0xFFFFFFFF
 SEND_OK, SEND_ERR_FRAGMENT_SIZE, SEND_ERR_RANGE = range(3)
+# include/wsframe_amd_deflate.h: the entry and the two results of batch_inflate_device / inflate_host, kinds, status values
+INFLATE_MSG_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u8"), ("kind", "<u4"), ("reserved", "<u4")])
+INFLATE_MSGRES_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("status", "<u4"), ("reserved", "<u4")])
+INFLATE_RES_DTYPE = np.dtype([("out_len", "<u8"), ("n_msgs", "<u4"), ("status", "<u4"), ("first_bad", "<u4"),
+                              ("close_status", "<u4")])
+assert INFLATE_MSG_DTYPE.itemsize == INFLATE_MSGRES_DTYPE.itemsize == INFLATE_RES_DTYPE.itemsize == 24
+INFLATE_SKIP = INFLATE_NONE = 0xFFFFFFFF
+INFLATE_RAW = 1
+(INFLATE_OK, INFLATE_ERR_DATA, INFLATE_ERR_TOO_BIG, INFLATE_ERR_OUT_SPACE, INFLATE_ERR_RANGE,
+ INFLATE_NOT_RUN) = range(6)
 # include/wsframe_amd_client.h: the entry, the two descriptors, the flags and the reasons of the client handshake
 CLI_ENTRY_DTYPE = np.dtype([("path_off", "<u8"), ("proto_off", "<u8"), ("host_off", "<u8"), ("path_len", "<u4"),
                             ("proto_len", "<u4"), ("host_len", "<u4"), ("reserved", "<u4", (3,))])
@@ -407,6 +417,55 @@ def send_host(src, msg, frag_size=SEND_FRAG_DEFAULT, mask_key=None, tx_capacity=
     if n < 0:
         check(-1, "websocketframeSendHost", lib)
     return n, bytes(tx[:min(n, tx_capacity)]), moff[:len(msg)], out[0]
+
+
+def batch_inflate_device(src, msg, nmsg, max_msgs, dst, dst_off, dst_cap, msg_res, res, max_message_size=0, src_len=None,
+                         flags=0, stream=None):
+    """websocketframeBatchInflateDevice (libwsframe_amd_deflate.so) on torch CUDA tensors: src (uint8,
+    the compressed bodies), msg (uint8 >= 24*nseg*max_msgs: INFLATE_MSG_DTYPE records at s*max_msgs +
+    i), nmsg (int32 nseg), dst (uint8: the rooms), dst_off / dst_cap (int64 nseg: connection s owns
+    dst[dst_off[s]:dst_off[s] + dst_cap[s]]), msg_res (uint8 24*nseg*max_msgs: INFLATE_MSGRES_DTYPE),
+    res (uint8 24*nseg: INFLATE_RES_DTYPE). src_len defaults to src.numel(); async on `stream`."""
+    nseg = nmsg.numel()
+    assert msg.numel() * msg.element_size() >= 24 * nseg * max_msgs
+    assert msg_res.numel() * msg_res.element_size() >= 24 * nseg * max_msgs
+    assert res.numel() * res.element_size() >= 24 * nseg
+    assert dst_off.numel() * dst_off.element_size() >= 8 * nseg and dst_cap.numel() * dst_cap.element_size() >= 8 * nseg
+    lib = _lib.load_deflate_lib()
+    rc = lib.websocketframeBatchInflateDevice(_ptr(src), int(src.numel() if src_len is None else src_len), _ptr(msg), _ptr(nmsg),
+                                              nseg, int(max_msgs), int(max_message_size), int(flags), _ptr(dst), _ptr(dst_off),
+                                              _ptr(dst_cap), _ptr(msg_res), _ptr(res), _stream(stream))
+    check(rc, "websocketframeBatchInflateDevice", lib)
+
+
+def batch_inflate_list_from_messages_device(buf, desc, msg, nmsg, max_frames, inf_msg, stream=None):
+    """websocketframeBatchInflateListFromMessagesDevice: the inflate list (uint8 >= 24*nseg*max_frames)
+    from the wire buffer and what batch_reassemble_device left in desc, msg and nmsg; async on `stream`."""
+    nseg = nmsg.numel()
+    assert desc.numel() * desc.element_size() >= 32 * nseg * max_frames
+    assert msg.numel() * msg.element_size() >= 32 * nseg * max_frames
+    assert inf_msg.numel() * inf_msg.element_size() >= 24 * nseg * max_frames
+    lib = _lib.load_deflate_lib()
+    rc = lib.websocketframeBatchInflateListFromMessagesDevice(_ptr(buf), _ptr(desc), _ptr(msg), _ptr(nmsg), nseg,
+                                                              int(max_frames), _ptr(inf_msg), _stream(stream))
+    check(rc, "websocketframeBatchInflateListFromMessagesDevice", lib)
+
+
+def inflate_host(src, msg, dst_cap, max_message_size=0, flags=0):
+    """websocketframeInflateHost on one connection: src (numpy uint8), msg (INFLATE_MSG_DTYPE array).
+    Returns (the connection's output bytes, INFLATE_MSGRES_DTYPE records, INFLATE_RES_DTYPE record)."""
+    lib = _lib.load_deflate_lib()
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    msg = np.ascontiguousarray(msg, dtype=INFLATE_MSG_DTYPE)
+    dst = np.zeros(max(1, dst_cap), np.uint8)
+    mr = np.zeros(max(1, len(msg)), INFLATE_MSGRES_DTYPE)
+    out = np.zeros(1, INFLATE_RES_DTYPE)
+    n = lib.websocketframeInflateHost(src.ctypes.data if len(src) else None, len(src), msg.ctypes.data if len(msg) else None,
+                                      len(msg), int(max_message_size), int(flags), dst.ctypes.data, int(dst_cap),
+                                      mr.ctypes.data, out.ctypes.data)
+    if n < 0:
+        check(-1, "websocketframeInflateHost", lib)
+    return bytes(dst[:n]), mr[:len(msg)], out[0]
 
 
 def batch_handshake_device(buf, seg_off, seg_len, hs, flags=0, accept=None, resp=None, resp_off=None, resp_cap=0,
