@@ -85,7 +85,13 @@ DEFLATE_LIB_PATH = os.path.join(HERE, "libwsframe_amd_deflate.so")
 DEFLATE_EXPORTS = ["websocketframeBatchInflateDevice", "websocketframeBatchInflateListFromMessagesDevice",
                    "websocketframeInflateHost"]
 _deflate = None
-_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply, send, cli and deflate libraries keep their own copies
+# libwsframe_amd_pmd.so: everything libwsframe_amd_deflate.so exports plus the WSFRAME_AMD_PMD_EXPORT
+# entry points (include/wsframe_amd_compress.h)
+PMD_LIB_PATH = os.path.join(HERE, "libwsframe_amd_pmd.so")
+PMD_EXPORTS = ["websocketframeBatchDeflateDevice", "websocketframeBatchSendListFromDeflatedDevice",
+               "websocketframeBatchSendExtDevice", "websocketframeDeflateHost", "websocketframeSendExtHost"]
+_pmd = None
+_options = {}            # options set through set_option(): the ctl, text, proto, hs, reply, send, cli, deflate and pmd libraries keep their own copies
 # include/wsframe_amd_bench.h (libwsframe_amd_bench.so)
 BENCH_EXPORTS = ["websocketframeSynthDevice", "websocketframeSynthVerifyDevice", "websocketframeGpuCalibrate",
                  "websocketframeBenchLastError", "websocketframeSynthDeviceRange",
@@ -199,6 +205,8 @@ def set_option(name, value):
             _cli.websocketframeGpuSetOption(name.encode(), int(value))
         if _deflate is not None:
             _deflate.websocketframeGpuSetOption(name.encode(), int(value))
+        if _pmd is not None:
+            _pmd.websocketframeGpuSetOption(name.encode(), int(value))
     return rc
 
 
@@ -467,6 +475,53 @@ def load_deflate_lib():
     for name, value in _options.items():
         lib.websocketframeGpuSetOption(name.encode(), value)
     _deflate = lib
+    return lib
+
+
+def load_pmd_lib():
+    """libwsframe_amd_pmd.so: the permessage-deflate send side (websocketframeBatchDeflateDevice,
+    websocketframeBatchSendListFromDeflatedDevice, websocketframeBatchSendExtDevice and the host twins
+    websocketframeDeflateHost, websocketframeSendExtHost) next to the whole C ABI of
+    libwsframe_amd_deflate.so. A library of its own state, as load_deflate_lib(): the options set so
+    far are applied when it loads and forwarded afterwards."""
+    global _pmd
+    if _pmd is not None:
+        return _pmd
+    load_lib()
+    if not os.path.exists(PMD_LIB_PATH):
+        raise RuntimeError("libwsframe_amd_pmd.so not built: run __graft_entry__.build(); there is no fallback path")
+    lib = C.CDLL(PMD_LIB_PATH)
+    vp, u64, u32, i32 = C.c_void_p, C.c_ulonglong, C.c_uint, C.c_int
+    lib.websocketframeBatchDeflateDevice.restype = i32
+    lib.websocketframeBatchDeflateDevice.argtypes = [vp, u64, vp, vp, u32, u32, u64, u32, vp, vp, vp, vp, vp]
+    lib.websocketframeBatchSendListFromDeflatedDevice.restype = i32
+    lib.websocketframeBatchSendListFromDeflatedDevice.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    lib.websocketframeBatchSendExtDevice.restype = i32
+    lib.websocketframeBatchSendExtDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp]
+    lib.websocketframeDeflateHost.restype = C.c_longlong
+    lib.websocketframeDeflateHost.argtypes = [vp, u64, vp, u32, u64, u32, vp, vp, vp, vp]
+    lib.websocketframeSendExtHost.restype = C.c_longlong
+    lib.websocketframeSendExtHost.argtypes = [vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, vp]
+    lib.websocketframeBatchSendDevice.restype = i32
+    lib.websocketframeBatchSendDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp]
+    lib.websocketframeSendHost.restype = C.c_longlong
+    lib.websocketframeSendHost.argtypes = [vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, vp]
+    lib.websocketframeBatchReassembleDevice.restype = i32
+    lib.websocketframeBatchReassembleDevice.argtypes = [vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.websocketframeBatchInflateDevice.restype = i32
+    lib.websocketframeBatchInflateDevice.argtypes = [vp, u64, vp, vp, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]
+    lib.websocketframeBatchInflateListFromMessagesDevice.restype = i32
+    lib.websocketframeBatchInflateListFromMessagesDevice.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    lib.websocketframeInflateHost.restype = C.c_longlong
+    lib.websocketframeInflateHost.argtypes = [vp, u64, vp, u32, u64, u32, vp, u64, vp, vp]
+    lib.websocketframeGpuLastError.restype = C.c_char_p
+    lib.websocketframeGpuLastError.argtypes = []
+    lib.websocketframeGpuSetOption.restype = i32
+    lib.websocketframeGpuSetOption.argtypes = [C.c_char_p, C.c_longlong]
+    _env_options(lib)
+    for name, value in _options.items():
+        lib.websocketframeGpuSetOption(name.encode(), value)
+    _pmd = lib
     return lib
 
 

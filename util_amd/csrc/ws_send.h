@@ -27,6 +27,10 @@
 // Client role (a key per message): MASK bit, the 4 key bytes after the length, the body XORed by
 // byte position with the frame's key; fragment j's key is ws_send_frag_key(key, j) =
 // key ^ (j * 0x9E3779B9) (j's low 32 bits), so the fragments of one message do not share a key.
+// RSV1 (the ext entry points of include/wsframe_amd_compress.h, under WS_SEND_F_RSV1 only): an
+// entry whose T has WS_SEND_T_RSV1 set carries 0x40 on frame 0's first byte and on no other frame.
+// The bit travels in the record's type word (ws_send_rec_type: the opcode, and WS_SEND_REC_RSV1
+// for that bit); it changes no length.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -40,6 +44,9 @@
 #endif
 
 #define WS_SEND_NONE 0xFFFFFFFFu
+#define WS_SEND_F_RSV1 1u             // flags of the ext entry points: WEBSOCKET_SEND_FLAG_RSV1
+#define WS_SEND_T_RSV1 0x40u          // WebsocketSendMsg_t.type: WEBSOCKET_SEND_TYPE_RSV1
+#define WS_SEND_REC_RSV1 0x80000000u  // WsSendRec.type: frame 0 carries RSV1
 #define WS_SEND_SRC_MAX (1ull << 56)   // src_len above this is refused: 7 * L (the 3-byte frames of F = 7) stays a u64
 
 // ------------------------------------------------------------------------------------- geometry
@@ -78,8 +85,12 @@ struct WsSendRec {
     uint64_t src_off, len;        // its body in d_src
     uint64_t wire;                // its wire bytes
     uint32_t shard, key;          // the connection's shard; the message's key (client role)
-    uint32_t type, role;          // opcode of the first frame; 1: client role
+    uint32_t type, role;          // opcode of the first frame (| WS_SEND_REC_RSV1); 1: client role
 };
+// the record's type word of an entry's T under the call's flags
+WS_SEND_FN uint32_t ws_send_rec_type(uint32_t T, uint32_t flags) {
+    return (T & 0x0Fu) | ((flags & WS_SEND_F_RSV1) && (T & WS_SEND_T_RSV1) ? WS_SEND_REC_RSV1 : 0u);
+}
 
 // Where wire position p < r.wire of the message lies: its frame, the frame's first body byte in
 // the message, the position inside the frame, the frame's body bytes and H of them. One 64-bit
@@ -101,7 +112,8 @@ WS_SEND_FN WsSendLoc ws_send_locate(const WsSendRec& r, uint64_t p) {
 // byte w of frame f of the message: header, key or body
 WS_SEND_FN unsigned char ws_send_frame_byte(const WsSendRec& r, const unsigned char* src, const WsSendLoc& f, uint32_t w) {
     const uint32_t hl = f.hl, fk = ws_send_frag_key(r.key, f.j);
-    if (w == 0u) return (unsigned char)((f.body0 + f.flen == r.len ? 0x80u : 0u) | (f.j == 0 ? r.type & 0x0Fu : 0u));
+    if (w == 0u)
+        return (unsigned char)((f.body0 + f.flen == r.len ? 0x80u : 0u) | (f.j == 0 ? (r.type & 0x0Fu) | (r.type >> 31 << 6) : 0u));
     if (w < hl) {
         const uint32_t m = r.role ? 0x80u : 0u;
         if (w == 1u) return (unsigned char)((hl == 2u ? f.flen : (hl == 4u ? 126u : 127u)) | m);
@@ -190,9 +202,10 @@ WS_SEND_FN WebsocketSendResult_t ws_send_result(const WsSendSum& all) {
 // The whole rule for one connection (the host entry point; the kernels do the same in passes):
 // msg[0, nmsg), keys (NULL: server role) one per message slot, tx[0, cap) the wire bytes,
 // msg_tx_off (may be NULL) every message's first wire byte. Returns the full length.
-WS_SEND_FN uint64_t ws_send_connection(const unsigned char* src, uint64_t src_len, const WebsocketSendMsg_t* msg,
-                                       uint32_t nmsg, uint32_t F, const uint32_t* keys, unsigned char* tx, uint64_t cap,
-                                       uint64_t* msg_tx_off, WebsocketSendResult_t* out) {
+// flags: 0, or WS_SEND_F_RSV1 (the ext entry point).
+WS_SEND_FN uint64_t ws_send_connection_ext(const unsigned char* src, uint64_t src_len, const WebsocketSendMsg_t* msg,
+                                           uint32_t nmsg, uint32_t F, const uint32_t* keys, uint32_t flags, unsigned char* tx,
+                                           uint64_t cap, uint64_t* msg_tx_off, WebsocketSendResult_t* out) {
     const uint32_t role = keys ? 1u : 0u, shard = ws_send_shard(F, role);
     WsSendSum all = ws_send_sum_none();
     for (uint32_t i = 0; i < nmsg; ++i) all = ws_send_comb(all, ws_send_sum_msg(msg[i], i, src_len, F, role));
@@ -202,11 +215,16 @@ WS_SEND_FN uint64_t ws_send_connection(const unsigned char* src, uint64_t src_le
         if (msg_tx_off) msg_tx_off[i] = off;
         if (out->status != WEBSOCKET_SEND_OK || msg[i].type == WEBSOCKET_SEND_SKIP) continue;
         WsSendRec r = {off, msg[i].src_off, msg[i].len, ws_send_geo(msg[i].len, shard, role).wire, shard,
-                       keys ? keys[i] : 0u, msg[i].type, role};
+                       keys ? keys[i] : 0u, ws_send_rec_type(msg[i].type, flags), role};
         for (uint64_t p = 0; p < r.wire && off + p < cap; ++p) tx[off + p] = ws_send_byte(r, src, p);
         off += r.wire;
     }
     return off;
+}
+WS_SEND_FN uint64_t ws_send_connection(const unsigned char* src, uint64_t src_len, const WebsocketSendMsg_t* msg,
+                                       uint32_t nmsg, uint32_t F, const uint32_t* keys, unsigned char* tx, uint64_t cap,
+                                       uint64_t* msg_tx_off, WebsocketSendResult_t* out) {
+    return ws_send_connection_ext(src, src_len, msg, nmsg, F, keys, 0u, tx, cap, msg_tx_off, out);
 }
 
 // ------------------------------------------------------------------------------ kernel scratch

@@ -1,5 +1,6 @@
 // ws_send.hip — websocketframeBatchSendDevice, websocketframeBatchSendListFromMessagesDevice and
-// websocketframeSendHost (include/wsframe_amd_send.h): every connection's messages fragmented,
+// websocketframeSendHost (include/wsframe_amd_send.h), and their ext twins that can set RSV1
+// (include/wsframe_amd_compress.h: the same kernels, one bit in the record): every connection's messages fragmented,
 // framed and packed into its wire bytes, for gfx950. The rule, the closed-form lengths, the byte
 // function, the slot summary and its combine, the record and the workspace layout are ws_send.h's
 // (one definition, host-tested). No per-frame record exists anywhere: a frame is found inside its
@@ -35,6 +36,7 @@
 
 #include "ws_scan.h"
 #include "ws_send.h"
+#include "../../include/wsframe_amd_compress.h"   // the ext entry points (RSV1): declared there, built here
 
 #define SEND_T 256                       // threads per block: slots per tile, connections per segs block
 #define SEND_BLOCKS_PER_CU 8             // the tile kernels' grid
@@ -43,6 +45,7 @@
 #define SEND_LDS_RECS 2048u              // record offsets staged per piece (8 KiB of LDS)
 
 static_assert(SEND_T == WS_SEND_T && SEND_T * SEND_U * 16 == SEND_PIECE, "a block covers one piece");
+static_assert(WS_SEND_F_RSV1 == WEBSOCKET_SEND_FLAG_RSV1 && WS_SEND_T_RSV1 == WEBSOCKET_SEND_TYPE_RSV1, "ws_send.h restates the public bits");
 static_assert(sizeof(WsSendSum) == 32 && sizeof(WsSendRec) == 48 && sizeof(WebsocketSendResult_t) == 32 &&
                   sizeof(WebsocketSendMsg_t) == 24,
               "record sizes");
@@ -144,8 +147,8 @@ __global__ __launch_bounds__(1024) void ws_send_offs(u64* bo, u32 nb, u64* total
 __global__ __launch_bounds__(SEND_T) void ws_send_recs(const WebsocketSendMsg_t* msg, const u32* nmsg, const u32* frag,
                                                        const u32* keys, u32 nseg, u32 nslots, u32 max_msgs, u64 src_len,
                                                        u32 ntiles, const WsSendSum* agg, const WebsocketSendResult_t* res,
-                                                       const u64* bo64, const u64* loc, u64 cap, u32 lead, WsSendRec* rec,
-                                                       u32* ptr, u64* tx_off, u64* msg_tx_off) {
+                                                       const u64* bo64, const u64* loc, u64 cap, u32 lead, u32 flags,
+                                                       WsSendRec* rec, u32* ptr, u64* tx_off, u64* msg_tx_off) {
     __shared__ WsSendSum wsum[SEND_T / 64];
     const u64 total = tx_off[nseg], limit = total < cap ? total : cap;
     const u64 np = ws_send_pieces(limit, lead);
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(SEND_T) void ws_send_recs(const WebsocketSendMsg_t*
         r.wire = ok && m.sum.nmsg ? m.sum.bytes : 0ull;
         r.shard = m.shard;
         r.key = m.key;
-        r.type = m.m.type;
+        r.type = ws_send_rec_type(m.m.type, flags);
         r.role = keys ? 1u : 0u;
         ws_st(rec + m.q, r);
         if (m.i == 0) tx_off[m.s] = base;
@@ -329,29 +332,35 @@ __global__ __launch_bounds__(SEND_T) void ws_send_list(const WebsocketFrameDesc_
     o[2] = (u64)type;
 }
 
-extern "C" WSFRAME_AMD_SEND_EXPORT int websocketframeBatchSendDevice(
-    const unsigned char* d_src, unsigned long long src_len, const WebsocketSendMsg_t* d_msg, const unsigned int* d_nmsg,
-    unsigned int nseg, unsigned int max_msgs, const unsigned int* d_frag_size, const unsigned int* d_mask_key,
-    unsigned int flags, unsigned char* d_tx, unsigned long long tx_capacity, unsigned long long* d_tx_off,
-    unsigned long long* d_msg_tx_off, WebsocketSendResult_t* d_send_res, void* hip_stream) {
-    if (flags) return ws_set_msg("websocketframeBatchSendDevice: unknown flag");
-    if (max_msgs == 0) return ws_set_msg("websocketframeBatchSendDevice: invalid argument (max_msgs 0)");
+// the batch send behind both entry points: `who` names the caller in error texts, flags is 0 or
+// WEBSOCKET_SEND_FLAG_RSV1 (checked by the caller)
+static int send_batch(const char* who, const unsigned char* d_src, unsigned long long src_len, const WebsocketSendMsg_t* d_msg,
+                      const unsigned int* d_nmsg, unsigned int nseg, unsigned int max_msgs, const unsigned int* d_frag_size,
+                      const unsigned int* d_mask_key, unsigned int flags, unsigned char* d_tx, unsigned long long tx_capacity,
+                      unsigned long long* d_tx_off, unsigned long long* d_msg_tx_off, WebsocketSendResult_t* d_send_res,
+                      void* hip_stream) {
+    char text[160];
+    auto fail = [&](const char* what) {
+        snprintf(text, sizeof text, "%s: %s", who, what);
+        return ws_set_msg(text);
+    };
+    if (max_msgs == 0) return fail("invalid argument (max_msgs 0)");
     if (!d_tx_off || (!d_tx && tx_capacity) || (nseg && (!d_src || !d_msg || !d_nmsg || !d_send_res)))
-        return ws_set_msg("websocketframeBatchSendDevice: invalid argument (NULL pointer)");
+        return fail("invalid argument (NULL pointer)");
     if (reinterpret_cast<uintptr_t>(d_send_res) & 15)
-        return ws_set_msg("websocketframeBatchSendDevice: d_send_res not 16-B aligned");
+        return fail("d_send_res not 16-B aligned");
     if ((reinterpret_cast<uintptr_t>(d_msg) | reinterpret_cast<uintptr_t>(d_tx_off) | reinterpret_cast<uintptr_t>(d_msg_tx_off)) & 7)
-        return ws_set_msg("websocketframeBatchSendDevice: d_msg/d_tx_off/d_msg_tx_off not 8-B aligned");
+        return fail("d_msg/d_tx_off/d_msg_tx_off not 8-B aligned");
     if ((reinterpret_cast<uintptr_t>(d_nmsg) | reinterpret_cast<uintptr_t>(d_frag_size) | reinterpret_cast<uintptr_t>(d_mask_key)) & 3)
-        return ws_set_msg("websocketframeBatchSendDevice: d_nmsg/d_frag_size/d_mask_key not 4-B aligned");
-    if (src_len > WS_SEND_SRC_MAX) return ws_set_msg("websocketframeBatchSendDevice: src_len > 2^56");
-    if (tx_capacity > (1ull << 44)) return ws_set_msg("websocketframeBatchSendDevice: tx_capacity > 2^44");
+        return fail("d_nmsg/d_frag_size/d_mask_key not 4-B aligned");
+    if (src_len > WS_SEND_SRC_MAX) return fail("src_len > 2^56");
+    if (tx_capacity > (1ull << 44)) return fail("tx_capacity > 2^44");
     const u64 nslots64 = (u64)nseg * max_msgs;
-    if (nslots64 > (1ull << 30)) return ws_set_msg("websocketframeBatchSendDevice: nseg * max_msgs > 2^30");
+    if (nslots64 > (1ull << 30)) return fail("nseg * max_msgs > 2^30");
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     if (nseg == 0) {
         const hipError_t e = hipMemsetAsync(d_tx_off, 0, 8, st);
-        return e == hipSuccess ? 0 : ws_set_err("websocketframeBatchSendDevice memset", e);
+        return e == hipSuccess ? 0 : (snprintf(text, sizeof text, "%s memset", who), ws_set_err(text, e));
     }
     const u32 nslots = (u32)nslots64;
     const WsSendLayout L = ws_send_layout(nseg, max_msgs, tx_capacity);
@@ -376,13 +385,33 @@ extern "C" WSFRAME_AMD_SEND_EXPORT int websocketframeBatchSendDevice(
     hipLaunchKernelGGL(ws_send_segs, dim3(L.nb), dim3(SEND_T), 0, st, nseg, max_msgs, agg, tail, d_send_res, loc, bo64);
     hipLaunchKernelGGL(ws_send_offs, dim3(1), dim3(1024), 0, st, bo64, L.nb, tx_off + nseg);
     hipLaunchKernelGGL(ws_send_recs, dim3(grid), dim3(SEND_T), 0, st, d_msg, d_nmsg, d_frag_size, d_mask_key, nseg, nslots,
-                       max_msgs, (u64)src_len, L.ntiles, agg, d_send_res, bo64, loc, (u64)tx_capacity, lead, rec, ptr, tx_off,
+                       max_msgs, (u64)src_len, L.ntiles, agg, d_send_res, bo64, loc, (u64)tx_capacity, lead, flags, rec, ptr, tx_off,
                        reinterpret_cast<u64*>(d_msg_tx_off));
     if (tx_capacity)
         hipLaunchKernelGGL(ws_send_emit, dim3((u32)L.npieces), dim3(SEND_T), 0, st, d_src, (u64)src_len, nseg, nslots, rec, ptr, tx_off, d_tx,
                            (u64)tx_capacity, lead);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : ws_set_err("websocketframeBatchSendDevice launch", e);
+    return e == hipSuccess ? 0 : (snprintf(text, sizeof text, "%s launch", who), ws_set_err(text, e));
+}
+
+extern "C" WSFRAME_AMD_SEND_EXPORT int websocketframeBatchSendDevice(
+    const unsigned char* d_src, unsigned long long src_len, const WebsocketSendMsg_t* d_msg, const unsigned int* d_nmsg,
+    unsigned int nseg, unsigned int max_msgs, const unsigned int* d_frag_size, const unsigned int* d_mask_key,
+    unsigned int flags, unsigned char* d_tx, unsigned long long tx_capacity, unsigned long long* d_tx_off,
+    unsigned long long* d_msg_tx_off, WebsocketSendResult_t* d_send_res, void* hip_stream) {
+    if (flags) return ws_set_msg("websocketframeBatchSendDevice: unknown flag");
+    return send_batch("websocketframeBatchSendDevice", d_src, src_len, d_msg, d_nmsg, nseg, max_msgs, d_frag_size, d_mask_key, 0u, d_tx,
+                      tx_capacity, d_tx_off, d_msg_tx_off, d_send_res, hip_stream);
+}
+
+extern "C" WSFRAME_AMD_PMD_EXPORT int websocketframeBatchSendExtDevice(
+    const unsigned char* d_src, unsigned long long src_len, const WebsocketSendMsg_t* d_msg, const unsigned int* d_nmsg,
+    unsigned int nseg, unsigned int max_msgs, const unsigned int* d_frag_size, const unsigned int* d_mask_key,
+    unsigned int flags, unsigned char* d_tx, unsigned long long tx_capacity, unsigned long long* d_tx_off,
+    unsigned long long* d_msg_tx_off, WebsocketSendResult_t* d_send_res, void* hip_stream) {
+    if (flags & ~WEBSOCKET_SEND_FLAG_RSV1) return ws_set_msg("websocketframeBatchSendExtDevice: unknown flag");
+    return send_batch("websocketframeBatchSendExtDevice", d_src, src_len, d_msg, d_nmsg, nseg, max_msgs, d_frag_size, d_mask_key, flags,
+                      d_tx, tx_capacity, d_tx_off, d_msg_tx_off, d_send_res, hip_stream);
 }
 
 extern "C" WSFRAME_AMD_SEND_EXPORT int websocketframeBatchSendListFromMessagesDevice(
@@ -414,4 +443,16 @@ extern "C" WSFRAME_AMD_SEND_EXPORT long long websocketframeSendHost(
     if (src_len > WS_SEND_SRC_MAX) return ws_set_msg("websocketframeSendHost: src_len > 2^56");
     return (long long)ws_send_connection(src, src_len, msg, nmsg, frag_size, mask_key, tx, tx_capacity,
                                          reinterpret_cast<uint64_t*>(msg_tx_off), out);
+}
+
+extern "C" WSFRAME_AMD_PMD_EXPORT long long websocketframeSendExtHost(
+    const unsigned char* src, unsigned long long src_len, const WebsocketSendMsg_t* msg, unsigned int nmsg,
+    unsigned int frag_size, const unsigned int* mask_key, unsigned int flags, unsigned char* tx,
+    unsigned long long tx_capacity, unsigned long long* msg_tx_off, WebsocketSendResult_t* out) {
+    if (flags & ~WEBSOCKET_SEND_FLAG_RSV1) return ws_set_msg("websocketframeSendExtHost: unknown flag");
+    if (!src || !out || (!msg && nmsg) || (!tx && tx_capacity))
+        return ws_set_msg("websocketframeSendExtHost: invalid argument (NULL pointer)");
+    if (src_len > WS_SEND_SRC_MAX) return ws_set_msg("websocketframeSendExtHost: src_len > 2^56");
+    return (long long)ws_send_connection_ext(src, src_len, msg, nmsg, frag_size, mask_key, flags, tx, tx_capacity,
+                                             reinterpret_cast<uint64_t*>(msg_tx_off), out);
 }

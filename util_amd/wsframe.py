@@ -84,6 +84,12 @@ INFLATE_RES_DTYPE = np.dtype([("out_len", "<u8"), ("n_msgs", "<u4"), ("status", 
 assert INFLATE_MSG_DTYPE.itemsize == INFLATE_MSGRES_DTYPE.itemsize == INFLATE_RES_DTYPE.itemsize == 24
 INFLATE_SKIP = INFLATE_NONE = 0xFFFFFFFF
 INFLATE_RAW = 1
+# include/wsframe_amd_compress.h (libwsframe_amd_pmd.so): a compress list is a send list (SEND_MSG_DTYPE)
+DEFLATE_MSG_DTYPE = SEND_MSG_DTYPE
+DEFLATE_MSGRES_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("status", "<u4"), ("reserved", "<u4")])
+(DEFLATE_DEFLATED, DEFLATE_PLAIN, DEFLATE_SKIPPED, DEFLATE_ERR_OUT_SPACE, DEFLATE_ERR_RANGE) = range(5)
+SEND_FLAG_RSV1 = 1
+SEND_TYPE_RSV1 = 0x40
 (INFLATE_OK, INFLATE_ERR_DATA, INFLATE_ERR_TOO_BIG, INFLATE_ERR_OUT_SPACE, INFLATE_ERR_RANGE,
  INFLATE_NOT_RUN) = range(6)
 # include/wsframe_amd_client.h: the entry, the two descriptors, the flags and the reasons of the client handshake
@@ -466,6 +472,97 @@ def inflate_host(src, msg, dst_cap, max_message_size=0, flags=0):
     if n < 0:
         check(-1, "websocketframeInflateHost", lib)
     return bytes(dst[:n]), mr[:len(msg)], out[0]
+
+
+def batch_deflate_device(src, msg, nmsg, max_msgs, dst, dst_off, dst_cap, msg_res, min_len=0, src_len=None, flags=0, stream=None):
+    """websocketframeBatchDeflateDevice (libwsframe_amd_pmd.so) on torch CUDA tensors: src (uint8, the
+    bodies), msg (uint8 >= 24*nseg*max_msgs: a send list, DEFLATE_MSG_DTYPE records at s*max_msgs +
+    i), nmsg (int32 nseg), dst (uint8: the rooms), dst_off / dst_cap (int64 nseg*max_msgs: slot q owns
+    dst[dst_off[q]:dst_off[q] + dst_cap[q]]), msg_res (uint8 24*nseg*max_msgs: DEFLATE_MSGRES_DTYPE).
+    src_len defaults to src.numel(); async on `stream`."""
+    nseg = nmsg.numel()
+    assert msg.numel() * msg.element_size() >= 24 * nseg * max_msgs
+    assert msg_res.numel() * msg_res.element_size() >= 24 * nseg * max_msgs
+    assert dst_off.numel() * dst_off.element_size() >= 8 * nseg * max_msgs
+    assert dst_cap.numel() * dst_cap.element_size() >= 8 * nseg * max_msgs
+    lib = _lib.load_pmd_lib()
+    rc = lib.websocketframeBatchDeflateDevice(_ptr(src), int(src.numel() if src_len is None else src_len), _ptr(msg), _ptr(nmsg),
+                                              nseg, int(max_msgs), int(min_len), int(flags), _ptr(dst), _ptr(dst_off),
+                                              _ptr(dst_cap), _ptr(msg_res), _stream(stream))
+    check(rc, "websocketframeBatchDeflateDevice", lib)
+
+
+def batch_send_list_from_deflated_device(msg, nmsg, max_msgs, msg_res, send_msg, stream=None):
+    """websocketframeBatchSendListFromDeflatedDevice: the send list (uint8 >= 24*nseg*max_msgs) of what
+    batch_deflate_device left in msg_res, DEFLATED entries marked SEND_TYPE_RSV1; async on `stream`."""
+    nseg = nmsg.numel()
+    assert msg.numel() * msg.element_size() >= 24 * nseg * max_msgs
+    assert msg_res.numel() * msg_res.element_size() >= 24 * nseg * max_msgs
+    assert send_msg.numel() * send_msg.element_size() >= 24 * nseg * max_msgs
+    lib = _lib.load_pmd_lib()
+    rc = lib.websocketframeBatchSendListFromDeflatedDevice(_ptr(msg), _ptr(nmsg), nseg, int(max_msgs), _ptr(msg_res),
+                                                           _ptr(send_msg), _stream(stream))
+    check(rc, "websocketframeBatchSendListFromDeflatedDevice", lib)
+
+
+def batch_send_ext_device(src, msg, nmsg, max_msgs, tx, tx_off, send_res, frag_size=None, mask_key=None, msg_tx_off=None,
+                          tx_capacity=None, src_len=None, flags=SEND_FLAG_RSV1, stream=None):
+    """websocketframeBatchSendExtDevice (libwsframe_amd_pmd.so): batch_send_device's arguments; under
+    flags = SEND_FLAG_RSV1 an entry whose type has SEND_TYPE_RSV1 carries RSV1 on its first frame."""
+    nseg = nmsg.numel()
+    assert msg.numel() * msg.element_size() >= 24 * nseg * max_msgs
+    assert tx_off.numel() * tx_off.element_size() >= 8 * (nseg + 1)
+    assert send_res.numel() * send_res.element_size() >= 32 * nseg
+    assert frag_size is None or frag_size.numel() * frag_size.element_size() >= 4 * nseg
+    assert mask_key is None or mask_key.numel() * mask_key.element_size() >= 4 * nseg * max_msgs
+    assert msg_tx_off is None or msg_tx_off.numel() * msg_tx_off.element_size() >= 8 * nseg * max_msgs
+    cap = (0 if tx is None else tx.numel()) if tx_capacity is None else tx_capacity
+    lib = _lib.load_pmd_lib()
+    rc = lib.websocketframeBatchSendExtDevice(_ptr(src), int(src.numel() if src_len is None else src_len), _ptr(msg), _ptr(nmsg),
+                                              nseg, int(max_msgs), _ptr(frag_size), _ptr(mask_key), int(flags), _ptr(tx),
+                                              int(cap), _ptr(tx_off), _ptr(msg_tx_off), _ptr(send_res), _stream(stream))
+    check(rc, "websocketframeBatchSendExtDevice", lib)
+
+
+def deflate_host(src, msg, dst_off, dst_cap, dst_len, min_len=0, flags=0, fill=0):
+    """websocketframeDeflateHost on one list: src (numpy uint8), msg (DEFLATE_MSG_DTYPE array), dst_off /
+    dst_cap (one room per entry, inside a destination of dst_len bytes preset to `fill`). Returns
+    (the destination as a numpy array, DEFLATE_MSGRES_DTYPE records, the C return value)."""
+    lib = _lib.load_pmd_lib()
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    msg = np.ascontiguousarray(msg, dtype=DEFLATE_MSG_DTYPE)
+    off = np.ascontiguousarray(dst_off, dtype=np.uint64)
+    cap = np.ascontiguousarray(dst_cap, dtype=np.uint64)
+    assert len(off) == len(cap) == len(msg)
+    dst = np.full(max(1, dst_len), fill, np.uint8)
+    mr = np.zeros(max(1, len(msg)), DEFLATE_MSGRES_DTYPE)
+    n = lib.websocketframeDeflateHost(src.ctypes.data if len(src) else None, len(src), msg.ctypes.data if len(msg) else None,
+                                      len(msg), int(min_len), int(flags), dst.ctypes.data, off.ctypes.data if len(msg) else None,
+                                      cap.ctypes.data if len(msg) else None, mr.ctypes.data if len(msg) else None)
+    if n < 0:
+        check(-1, "websocketframeDeflateHost", lib)
+    return dst[:dst_len], mr[:len(msg)], n
+
+
+def send_ext_host(src, msg, frag_size=SEND_FRAG_DEFAULT, mask_key=None, flags=SEND_FLAG_RSV1):
+    """websocketframeSendExtHost on one connection (send_host's arguments, sized by a first call).
+    Returns (the wire bytes, every message's offset, SEND_RES_DTYPE record)."""
+    lib = _lib.load_pmd_lib()
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    msg = np.ascontiguousarray(msg, dtype=SEND_MSG_DTYPE)
+    keys = None if mask_key is None else np.ascontiguousarray(mask_key, dtype=np.uint32)
+    kp = None if keys is None else keys.ctypes.data
+    out = np.zeros(1, SEND_RES_DTYPE)
+    moff = np.zeros(max(1, len(msg)), np.uint64)
+    sp = (src if len(src) else np.zeros(1, np.uint8)).ctypes.data
+    n = lib.websocketframeSendExtHost(sp, len(src), msg.ctypes.data, len(msg), int(frag_size), kp, int(flags), None, 0, None,
+                                      out.ctypes.data)
+    if n < 0:
+        check(-1, "websocketframeSendExtHost", lib)
+    tx = np.zeros(max(1, n), np.uint8)
+    n = lib.websocketframeSendExtHost(sp, len(src), msg.ctypes.data, len(msg), int(frag_size), kp, int(flags), tx.ctypes.data, n,
+                                      moff.ctypes.data, out.ctypes.data)
+    return bytes(tx[:n]), moff[:len(msg)], out[0]
 
 
 def batch_handshake_device(buf, seg_off, seg_len, hs, flags=0, accept=None, resp=None, resp_off=None, resp_cap=0,
