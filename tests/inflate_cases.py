@@ -28,9 +28,7 @@ class Bits:
 
     def code(self, code_len):
         code, n = code_len
-        for b in range(n - 1, -1, -1):
-            self.bits((code >> b) & 1, 1)
-        return self
+        return self.bits(int(format(code, "0%db" % n)[::-1], 2), n)
 
     def done(self):
         return self.v.to_bytes((self.n + 7) // 8, "little")

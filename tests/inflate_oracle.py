@@ -69,6 +69,7 @@ def batch(src, msg, nmsg, max_msgs, limit, dst_off, dst_cap, fill=0xEE):
     """the whole call: (MSGRES [nseg*max_msgs] with unwritten slots left at `fill` bytes, RES [nseg],
     [every connection's output bytes])"""
     nseg = len(nmsg)
+    src = bytes(src)                                          # once: connection() takes bytes as they are
     mr = np.frombuffer(bytes([fill]) * (24 * nseg * max_msgs), MSGRES_DTYPE).copy()
     res = np.zeros(nseg, RES_DTYPE)
     outs = []

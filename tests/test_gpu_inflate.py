@@ -46,9 +46,10 @@ def place(bodies, aligns=None):
 
 class Call:
     """the device buffers of one batch. conns: per connection [(src_off, len, kind)]; caps: every
-    connection's room (default: what its messages need); odd: region offsets that are no multiple of 16"""
+    connection's room (default: what its messages need); odd: region offsets that are no multiple of 16;
+    offs: every connection's region offset, ascending and at least GAP apart (default: packed)"""
 
-    def __init__(self, dev, src, conns, limit=0, caps=None, max_msgs=None, nmsg=None, odd=False, src_t=None):
+    def __init__(self, dev, src, conns, limit=0, caps=None, max_msgs=None, nmsg=None, odd=False, src_t=None, offs=None):
         self.dev, self.nseg, self.limit = dev, len(conns), limit
         self.mm = max_msgs or max([1] + [len(c) for c in conns])
         msg = np.zeros(self.nseg * self.mm, O.MSG_DTYPE)
@@ -62,10 +63,16 @@ class Call:
                 caps.append(sum(len(O.inflate_one(bytes(src[o:o + n]), limit)[1]) for o, n, k in c[:self.mm]
                                 if k == O.RAW and o + n <= len(src)))
         self.caps = np.array(caps, np.uint64)
-        offs, at = [], GAP + (5 if odd else 0)
-        for s in range(self.nseg):
-            offs.append(at)
-            at += int(self.caps[s]) + GAP + ((3 + 2 * s) % 16 if odd else 0)
+        if offs is None:
+            offs, at = [], GAP + (5 if odd else 0)
+            for s in range(self.nseg):
+                offs.append(at)
+                at += int(self.caps[s]) + GAP + ((3 + 2 * s) % 16 if odd else 0)
+        else:
+            at = GAP
+            for s in range(self.nseg):
+                assert int(offs[s]) >= at, "region %d overlaps the one before it or its sentinels" % s
+                at = int(offs[s]) + int(self.caps[s]) + GAP
         self.offs = np.array(offs, np.uint64)
         self.exp = O.batch(src, msg, self.nmsg, self.mm, limit, self.offs, self.caps, fill=O.FILL)
         self.src = T(src, dev) if src_t is None else src_t
